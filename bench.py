@@ -21,7 +21,12 @@ The encode configuration is webp.Encode's DefaultOptions (quality 75, method
 After the timed region the in-kernel dependency waits are checked
 (wg_encode_status / wg_decode_status: the last launch of each slot plus the
 library's device-wide count of timed-out waits, which covers every timed
-launch).  Then, untimed for `value`:
+launch).  A plain run (`bench.py --gpus 1 --steps K --warmup W`) then prints
+the result line (value, ms_per_step, the per-stage event times of the timed
+steps) and exits.  `--dump-outputs DIR` first writes what the last timed step
+computed (dump_outputs) as DIR/<name>.npy, so two builds can be compared
+output for output: the inputs depend on the arguments alone.  With `--full`,
+untimed for `value`:
   - `runs`: the median of --runs repeats of a short timed region, for the
     whole path and for the encode side and the decode side alone (BASELINE.md 2);
   - an isolated one-batch pass for each kernel's launch time (the roofline);
@@ -52,6 +57,7 @@ import socket
 import subprocess
 import sys
 import time
+import zlib
 
 import numpy as np
 import torch
@@ -75,7 +81,7 @@ BYTES_PER_PX = {
 KERNELS = {"import": "k_import", "analysis": "k_analysis", "segments": "k_segments", "encode": "k_encode_rows",
            "decode": "k_decode_split", "upsample": "k_upsample"}  # decode: set from wg_decode_kernel at report time
 CONTENTS = ("grad", "noise", "photo")
-BITSTREAMS = os.path.join(ROOT, "tests", "golden", "q75_1080p.npz")
+BITSTREAMS = "q75_1080p.npz"  # tests/golden/, read with tools.golden.load
 PMC_FILE = os.path.join(ROOT, "profiles", "pmc_traffic.json")
 VALU_FILE = os.path.join(ROOT, "profiles", "pmc_valu.json")
 # SQ passes over one 64 x 1080p k_encode_rows launch (tools/gpu_enc_pmc.sh): wave
@@ -167,6 +173,13 @@ def parse():
     p.add_argument("--steps", type=int, default=10)
     p.add_argument("--warmup", type=int, default=3)
     p.add_argument("--batch", type=int, default=64, help="frames per GPU per step (C4: 512 frames / 8 GPUs)")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also measure everything reported beside value: the medians (runs), the "
+                        "isolated kernel times and the roofline, the one-frame encodes, the copy ceiling, C3 / C5, "
+                        "the N > 1 gather and the CPU baseline; the options below shape these and need --full")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write the last timed step's outputs as DIR/<name>.npy (float32 / "
+                        "float64; large arrays as a fixed, seeded sample)")
     p.add_argument("--cpu-seconds", type=float, default=10.0, help="budget for the CPU baseline sample")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--slots", type=int, default=3, help="batches in flight (two HIP streams each)")
@@ -203,7 +216,8 @@ def frame_rgba(g):
 def parsed_bitstreams():
     """(dims, mb_info, coeffs) of the three libwebp q75 1080p bitstreams, parsed by the product parser."""
     from webp_amd import frames
-    z = np.load(BITSTREAMS)
+    from tools import golden
+    z = golden.load(BITSTREAMS)
     out = {}
     for k in CONTENTS:
         dims, mb, co = frames.vp8_parse(z[k].tobytes())
@@ -529,7 +543,7 @@ def single_frame_encode(device, reps=3):
     return {"frames": res, "critical_path_mb_steps": steps_cp}
 
 
-C3_STREAM = os.path.join(ROOT, "tests", "golden", "c3_4096_q75.npz")
+C3_STREAM = "c3_4096_q75.npz"  # tests/golden/, read with tools.golden.load
 C5_N = 4096
 # algorithmic HBM bytes per pixel of the C5 stages: ARGB in and
 # out (8), packed RGB in + Y / U / V out (4.5, SharpYUV), two planes in (2, SSIM)
@@ -565,7 +579,8 @@ def c3_decode(device, reps=10):
     wg_vp8_parse (timed apart), then reconstruct + loop filter and fancy
     upsample to NRGBA on the GPU; median device times over `reps`."""
     from webp_amd import _lib, frames
-    data = np.load(C3_STREAM)["webp"].tobytes()
+    from tools import golden
+    data = golden.load(C3_STREAM)["webp"].tobytes()
     t0 = time.perf_counter()
     dims, mb, co = frames.vp8_parse(data)
     parse_ms = (time.perf_counter() - t0) * 1e3
@@ -627,6 +642,96 @@ def c5_stages(device, reps=10):
     torch.cuda.synchronize()
     return {"workload": f"one {n}x{n} RGBA noise + gradient blend (SURVEY 8(d) C5), 1 GPU", "stages": out,
             "reps": reps}
+
+
+DUMP_SEED = 0x57454250
+DUMP_RECORDS = 4096      # wg_mb_enc records sampled from the batch (every field of each)
+DUMP_ELEMENTS = 1 << 20  # elements sampled from each plane / pixel array
+
+
+def dump_positions(name, n, m):
+    """The m positions (of n > m) that array `name` is sampled at: one from
+    each of m consecutive strata of the array, so they are distinct, ascending
+    and spread over the whole of it; drawn from a seed fixed by the name, the
+    same in every run."""
+    rng = np.random.default_rng([DUMP_SEED, zlib.crc32(name.encode())])
+    edges = np.arange(m + 1, dtype=np.int64) * n // m
+    return edges[:-1] + rng.integers(0, edges[1:] - edges[:-1])
+
+
+def dump_outputs(pipe, directory, rank=0, world=1):
+    """--dump-outputs: what a caller of the timed path receives from its last
+    step (the slot that step ran in), as DIR/<name>.npy -- the encode side's
+    wg_mb_enc records (one array per field), segment ids, per-frame segment
+    records and reconstruction, the decode side's planes and NRGBA.  Arrays
+    of more than DUMP_ELEMENTS elements are sampled at dump_positions
+    (records: DUMP_RECORDS whole records), the planes inside the visible
+    width x height; about 40 MB in all at the default batch.  8- and 16-bit
+    values are stored as float32, 32- and 64-bit fields (masks, the RD score)
+    as float64."""
+    f = pipe.frames
+    sl = pipe.slots[(pipe.k - 1) % len(pipe.slots)]
+    torch.cuda.synchronize()
+    os.makedirs(directory, exist_ok=True)
+    suffix = "" if world == 1 else f"_rank{rank}"
+
+    def save(name, a):
+        dt = np.float64 if a.dtype.itemsize >= 4 else np.float32
+        np.save(os.path.join(directory, name + suffix + ".npy"), np.ascontiguousarray(a, dtype=dt))
+
+    def sampled(name, t, m=DUMP_ELEMENTS):
+        if t.shape[0] > m:
+            t = t[torch.from_numpy(dump_positions(name, t.shape[0], m)).to(t.device)]
+        return t.cpu().numpy()
+
+    rows = sampled("enc", sl.enc_out, DUMP_RECORDS)
+    recs = rows.view(f.MB_ENC_DTYPE).reshape(-1)
+    for name in f.MB_ENC_DTYPE.names:
+        if not name.startswith("pad"):
+            save("enc_" + name, recs[name])
+    info = sl.seg_info.cpu().numpy().view(f.FRAME_SEGS_DTYPE).reshape(-1)
+    for name in f.FRAME_SEGS_DTYPE.names:
+        if not name.startswith("pad"):
+            save("frame_segs_" + name, info[name])
+    save("segment_ids", sampled("segment_ids", sl.seg_ids.reshape(-1)))
+    cw, ch = (W + 1) >> 1, (H + 1) >> 1
+    for name, t, w, h in (("recon_y", sl.rY, W, H), ("recon_u", sl.rU, cw, ch), ("recon_v", sl.rV, cw, ch),
+                          ("dec_y", sl.dY, W, H), ("dec_u", sl.dU, cw, ch), ("dec_v", sl.dV, cw, ch)):
+        save(name, sampled(name, t[:, :h, :w].reshape(-1)))
+    save("nrgba", sampled("nrgba", sl.out.reshape(-1)))
+
+
+def base_record(args, world, joined, elapsed, overlapped):
+    """The result line of a plain run; --full adds its measurements to it."""
+    return {
+        "metric": "MPixels/s encode+decode DSP path (1920x1080 q75)",
+        "value": round(aggregate_mpix_s(world, args.batch, args.steps, elapsed), 1),
+        "unit": "MPixels/s",
+        "n_gpus": world,
+        "ranks_joined": joined,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u8",
+        "data": "synthetic RGBA for the encode side, SURVEY 8(d) G / N / P (gradient, noise, the reference's "
+                "testdata/test_color.png tiled), a distinct seed per frame; libwebp q75 encodes of the three "
+                "contents, parsed by wg_vp8_parse, for the decode side",
+        "config": {"workload": f"{args.batch} x 1920x1080 frames per GPU per step (C2 frame, C4 per-GPU share): "
+                               "import+analysis+segments+MB RD loop (encode DSP) + reconstruct+loopfilter+upsample "
+                               "of q75 bitstreams (decode DSP)",
+                   "encoder": "webp.Encode DefaultOptions: q75 method 4 sns 50 filter 60 segments 4; segment "
+                              "ids and per-segment quantisers from assignSegments/setSegmentParams on the GPU "
+                              "(k_segments)",
+                   "frames_per_gpu": args.batch, "width": W, "height": H, "parallelism": f"frames sharded x{world}",
+                   "batches_in_flight": args.slots,
+                   "streams_per_batch": 2 if args.split else 1},
+        "value_stat": f"mean over the {args.steps} timed steps (the contract's K-step region)",
+        "full": bool(args.full),
+        "stage_ms_overlapped": {k: round(v, 3) for k, v in overlapped.items()},
+    }
 
 
 def free_port():
@@ -722,6 +827,14 @@ def main():
     elapsed = timed_region(pipe.step, args.steps, args.warmup, world, torch.cuda.synchronize, device)
     overlapped = pipe.stage_ms()
     pipe.check_status()  # raises if any launch so far hit an in-kernel wait timeout
+    if args.dump_outputs:
+        dump_outputs(pipe, args.dump_outputs, rank, world)
+    if not args.full:  # a plain run: the headline figure alone
+        if rank == 0:
+            print(json.dumps(base_record(args, world, joined, elapsed, overlapped)), flush=True)
+        if world > 1:
+            torch.distributed.destroy_process_group()
+        return
     runs = median_runs(pipe, args.runs, args.run_steps, world, device) if args.runs > 0 else None
     pipe.check_status()
     iso = isolated_stage_ms(rgba, mb, co, args.batch, device, args.iso_steps)
@@ -742,7 +855,6 @@ def main():
     torch.cuda.synchronize()
 
     if rank == 0:
-        value = aggregate_mpix_s(world, args.batch, args.steps, elapsed)
         step_ms = elapsed / args.steps * 1e3
         dominant = max(iso, key=iso.get)
         px_rank_step = args.batch * W * H
@@ -754,35 +866,11 @@ def main():
         achieved = alg / (iso[dominant] / 1e3) / 1e9
         traffic, traffic_src = pmc_traffic(kernel)
         model = slot_model(iso[dominant], args.batch) if kernel == "k_encode_rows" else None
-        rec = {
-            "metric": "MPixels/s encode+decode DSP path (1920x1080 q75)",
-            "value": round(value, 1),
-            "unit": "MPixels/s",
-            "n_gpus": world,
-            "ranks_joined": joined,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(step_ms, 3),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u8",
-            "data": "synthetic RGBA for the encode side, SURVEY 8(d) G / N / P (gradient, noise, the reference's "
-                    "testdata/test_color.png tiled), a distinct seed per frame; libwebp q75 encodes of the three "
-                    "contents, parsed by wg_vp8_parse, for the decode side",
-            "config": {"workload": f"{args.batch} x 1920x1080 frames per GPU per step (C2 frame, C4 per-GPU share): "
-                                   "import+analysis+segments+MB RD loop (encode DSP) + reconstruct+loopfilter+upsample "
-                                   "of q75 bitstreams (decode DSP)",
-                       "encoder": "webp.Encode DefaultOptions: q75 method 4 sns 50 filter 60 segments 4; segment "
-                                  "ids and per-segment quantisers from assignSegments/setSegmentParams on the GPU "
-                                  "(k_segments)",
-                       "frames_per_gpu": args.batch, "width": W, "height": H, "parallelism": f"frames sharded x{world}",
-                       "batches_in_flight": args.slots,
-                       "streams_per_batch": 2 if args.split else 1},
-            "value_stat": f"mean over the {args.steps} timed steps (the contract's K-step region); medians in `runs`",
+        rec = base_record(args, world, joined, elapsed, overlapped)
+        rec["value_stat"] += "; medians in `runs`"
+        rec.update({
             "runs": runs,
             "stage_ms_isolated": {k: round(v, 3) for k, v in iso.items()},
-            "stage_ms_overlapped": {k: round(v, 3) for k, v in overlapped.items()},
             "roofline": {"kernel": kernel, "bound": bound_of(achieved / HBM_PEAK_GBS, model), "peak_kind": "hbm",
                          "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
                          "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
@@ -805,7 +893,7 @@ def main():
                                    "GB/s": round(BYTES_PER_PX[k] * px_rank_step / (v / 1e3) / 1e9, 1),
                                    "frac": round(BYTES_PER_PX[k] * px_rank_step / (v / 1e3) / 1e9 / HBM_PEAK_GBS, 4)}
                                for k, v in iso.items()},
-        }
+        })
         if c2 is not None:
             slow = max(c2["frames"].values(), key=lambda r: r["rd_ms"])
             rec["roofline"]["critical_path"] = {

@@ -20,7 +20,7 @@ sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 
 import libwebp_ref as L  # noqa: E402
-from tools import synth  # noqa: E402
+from tools import golden, synth  # noqa: E402
 
 REF_PNG = "/root/reference/testdata/test.png"
 
@@ -62,6 +62,7 @@ def main():
     out["ssim_value2"] = np.array([L.plane_ssim(g, out["ssim_d"])], np.float64)
     np.savez_compressed(os.path.join(HERE, "libwebp_fixtures.npz"), **out)
     make_c1_fixture(img)
+    make_test_color_png()
     make_bench_bitstreams()
     make_decode_fixtures(img)
     make_sharpyuv_fixtures(img)
@@ -133,6 +134,21 @@ def make_c1_fixture(img):
     print("wrote", path, os.path.getsize(path), "bytes")
 
 
+def report_split(path):
+    """A fixture over the 1 MiB limit for a committed file is stored in parts (tools/golden.py)."""
+    size = os.path.getsize(path)
+    written = golden.split(os.path.basename(path), os.path.dirname(path))
+    print("wrote", path, size, "bytes as", ", ".join(os.path.basename(p) for p in written))
+
+
+def make_test_color_png():
+    """SURVEY 8(d) "P": the bytes of the reference's testdata/test_color.png,
+    which tools/synth.py decodes and tiles (photo_rgba)."""
+    path = os.path.join(HERE, "test_color_png.npz")
+    np.savez(path, png=np.frombuffer(open(C3_PNG, "rb").read(), np.uint8))
+    report_split(path)
+
+
 def make_bench_bitstreams():
     """libwebp 1.6.0 q75 (WebPEncodeRGBA defaults) encodes of 1920x1080
     contents -- gradient, noise seed 1, photo (test_color.png tiled, seed 0;
@@ -146,7 +162,7 @@ def make_bench_bitstreams():
            "blobs": L.encode_lossy(synth.blobs_rgba(w, h, seed=2), 75.0)}
     path = os.path.join(HERE, "q75_1080p.npz")
     np.savez(path, **{k: np.frombuffer(bytes(v), np.uint8) for k, v in out.items()})
-    print("wrote", path, os.path.getsize(path), "bytes")
+    report_split(path)
 
 
 C3_PNG = "/root/reference/testdata/test_color.png"
@@ -175,7 +191,7 @@ def make_c3_bitstream():
     path = os.path.join(HERE, "c3_4096_q75.npz")
     np.savez(path, webp=np.frombuffer(bytes(data), np.uint8), rgba_sha256=sha(rgba), y_sha256=sha(Y),
              u_sha256=sha(U), v_sha256=sha(V))
-    print("wrote", path, os.path.getsize(path), "bytes")
+    report_split(path)
 
 
 REF_TESTDATA = ["blue_16x16_lossy.webp", "red_4x4_lossy.webp", "red_4x4_lossless.webp",

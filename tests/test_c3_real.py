@@ -18,9 +18,10 @@ import pytest
 
 import oracle as O
 from test_oracle import libwebp_skip_rule
+from tools import golden
 from webp_amd import frames
 
-Z = np.load(os.path.join(os.path.dirname(__file__), "golden", "c3_4096_q75.npz"))
+Z = golden.load("c3_4096_q75.npz")
 W = H = 4096
 
 

@@ -12,6 +12,8 @@ records, the decoded planes and the NRGBA).  Every frame's encode input is
 distinct (bench.frame_rgba: content g % 3, seed g); the decode side replays
 the three contents' streams, so every other frame's decoded planes must equal
 those of the first frame of its content byte for byte."""
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -81,3 +83,43 @@ def test_bench_batch_matches_oracle(ran):
                 assert (p[i] == p[r]).all(), (s, i)
         raw = sl.enc_out.cpu().numpy().reshape(64, -1)
         assert len({raw[i].tobytes() for i in range(64)}) == 64, s
+
+
+def test_dump_outputs_sample_the_last_step(ran, tmp_path):
+    """bench.py --dump-outputs: float32 / float64 .npy files of at most 64 MB in
+    all, identical from one dump to the next, holding the last step's slot:
+    whole arrays where they are small, the values at bench.dump_positions
+    where they are sampled."""
+    from webp_amd import frames
+    _, _, pipe = ran
+    a, b = str(tmp_path / "a"), str(tmp_path / "b")
+    bench.dump_outputs(pipe, a)
+    bench.dump_outputs(pipe, b)
+    names = sorted(os.listdir(a))
+    assert names == sorted(os.listdir(b))
+    assert sum(os.path.getsize(os.path.join(a, n)) for n in names) <= 64 * 1000 * 1000
+    got = {n[:-4]: np.load(os.path.join(a, n)) for n in names}
+    for n in names:
+        assert n.endswith(".npy") and got[n[:-4]].dtype in (np.float32, np.float64), n
+        assert np.array_equal(got[n[:-4]], np.load(os.path.join(b, n))), n
+    sl = pipe.slots[(pipe.k - 1) % len(pipe.slots)]
+    W, H = bench.W, bench.H
+    cw, ch = (W + 1) // 2, (H + 1) // 2
+    planes = {"recon_y": sl.rY[:, :H, :W], "recon_u": sl.rU[:, :ch, :cw], "recon_v": sl.rV[:, :ch, :cw],
+              "dec_y": sl.dY[:, :H, :W], "dec_u": sl.dU[:, :ch, :cw], "dec_v": sl.dV[:, :ch, :cw], "nrgba": sl.out,
+              "segment_ids": sl.seg_ids}
+    for name, t in planes.items():
+        flat = t.cpu().numpy().reshape(-1)
+        if flat.size > bench.DUMP_ELEMENTS:
+            flat = flat[bench.dump_positions(name, flat.size, bench.DUMP_ELEMENTS)]
+        assert got[name].dtype == np.float32 and np.array_equal(got[name], flat), name
+    recs = sl.enc_out.cpu().numpy().view(frames.MB_ENC_DTYPE).reshape(-1)
+    recs = recs[bench.dump_positions("enc", recs.size, bench.DUMP_RECORDS)]
+    for f in FIELDS:
+        assert np.array_equal(got["enc_" + f], recs[f]), f
+    assert got["enc_score"].dtype == np.float64 and got["enc_coeffs"].shape == (bench.DUMP_RECORDS, 400)
+    info = sl.seg_info.cpu().numpy().view(frames.FRAME_SEGS_DTYPE).reshape(-1)
+    for f in frames.FRAME_SEGS_DTYPE.names:
+        if not f.startswith("pad"):
+            assert np.array_equal(got["frame_segs_" + f], info[f]), f
+    assert len(got) == len(planes) + len(FIELDS) + len(frames.FRAME_SEGS_DTYPE.names) - 2

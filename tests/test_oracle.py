@@ -8,10 +8,13 @@
    product's host parser (wg_vp8_parse, no GPU), reconstructed + loop-filtered
    by the oracle, compared with libwebp's normative WebPDecodeYUV.  This pins
    the oracle's predictors, inverse transforms and loop filters (A2-A13).
-4. Where the reference checkout is present (build container only), verbatim
-   reference tables are re-read and compared.
+4. Reference tables are compared by the digests recorded from them
+   (tests/golden/reference_tables.json) and, where the reference checkout is
+   present, re-read and compared value for value.
 """
 import ctypes
+import hashlib
+import json
 import os
 import re
 
@@ -20,6 +23,7 @@ import pytest
 
 import oracle as O
 from conftest import REFERENCE
+from tools import golden
 
 GOLD = np.load(os.path.join(os.path.dirname(__file__), "golden", "libwebp_fixtures.npz"))
 DEC = np.load(os.path.join(os.path.dirname(__file__), "golden", "libwebp_decode.npz"))
@@ -60,7 +64,7 @@ def test_bench_bitstreams_vs_libwebp(content):
     if not L.available:
         pytest.skip("Pillow libwebp not present")
     from webp_amd import frames
-    data = np.load(os.path.join(os.path.dirname(__file__), "golden", "q75_1080p.npz"))[content].tobytes()
+    data = golden.load("q75_1080p.npz")[content].tobytes()
     dims, mb, co = frames.vp8_parse(data)
     assert (dims["width"], dims["height"], dims["filter_type"]) == (1920, 1080, 2)
     y, u, v = O.decode_frame(libwebp_skip_rule(mb), co, 2, dims["mbw"], dims["mbh"])
@@ -198,11 +202,19 @@ def test_ssim_identity():
     assert abs(O.plane_ssim(p, p) - p.size) < 1e-6 * p.size
 
 
-# ---------------- reference tables (build container only) ----------------
+# ---------------- reference tables ----------------
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="reference checkout not present")
 def test_inv_alpha_table_is_floor_division():
-    """yuv.go:343-447 kInvAlpha[a] == floor(2^19 / a): the oracle and the GPU compute it."""
+    """yuv.go:343-447 kInvAlpha[a] == floor(2^19 / a): the oracle and the GPU compute it.
+    Checked against the length and SHA-256 recorded from the table
+    (tests/golden/reference_tables.json, tools/gen_vp8_tables.py) and, where
+    the reference checkout is present, against the table itself."""
+    pin = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "reference_tables.json")))["inv_alpha"]
+    want = [0] + [(1 << 19) // a for a in range(1, 1021)]
+    text = ",".join(str(v) for v in want)
+    assert pin == {"n": 1021, "sha256": hashlib.sha256(text.encode()).hexdigest()}
+    if not os.path.isdir(REFERENCE):
+        return
     src = open(os.path.join(REFERENCE, "internal/dsp/yuv.go")).read()
     body = re.search(r"var kInvAlpha = \[4\*0xff \+ 1\]uint32\{(.*?)\n\}", src, re.S).group(1)
     vals = [int(x) for x in re.findall(r"\d+", re.sub(r"//.*", "", body))]

@@ -18,7 +18,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import oracle as O  # noqa: E402
-from tools import synth  # noqa: E402
+from tools import golden, synth  # noqa: E402
 from webp_amd import frames  # noqa: E402
 
 REPS = int(os.environ.get("REPS", "5"))
@@ -54,8 +54,7 @@ def decode_case(n_img, w, h):
 
 def decode_real():
     import time
-    z = np.load(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden",
-                             "c3_4096_q75.npz"))
+    z = golden.load("c3_4096_q75.npz")
     data = z["webp"].tobytes()
     t0 = time.perf_counter()
     dims, mb, co = frames.vp8_parse(data)

@@ -10,13 +10,13 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
+from tools import golden  # noqa: E402
 from tools.bench_c3 import timed  # noqa: E402
 from webp_amd import frames  # noqa: E402
 
 
 def main():
-    z = np.load(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden",
-                             "c3_4096_q75.npz"))
+    z = golden.load("c3_4096_q75.npz")
     dims, mb, co = frames.vp8_parse(z["webp"].tobytes())
     mbw, mbh = dims["mbw"], dims["mbh"]
     mbt = frames.mb_info_tensor(mb)

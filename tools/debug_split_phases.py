@@ -7,7 +7,7 @@ synthetic macroblocks."""
 import ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
-from tools import synth
+from tools import golden, synth
 from webp_amd import _lib, frames
 B = int(os.environ.get("BATCH", "1"))
 MBW, MBH = (120, 68) if os.environ.get("SIZE") == "1080" else (256, 256)
@@ -19,8 +19,7 @@ REAL = os.environ.get("REAL") == "1"
 cases = [("real", None)] if REAL else [(0.5, 2), (0.0, 2), (1.0, 2)]
 for p_i4, ft in cases:
     if REAL:
-        z = np.load(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden",
-                                 "c3_4096_q75.npz"))
+        z = golden.load("c3_4096_q75.npz")
         dims, mb, co = frames.vp8_parse(z["webp"].tobytes())
         ft, MBW, MBH, B = dims["filter_type"], dims["mbw"], dims["mbh"], 1
         mbt, cot = frames.mb_info_tensor(mb), torch.from_numpy(co).cuda()

@@ -18,7 +18,7 @@ for v in $VARIANTS; do
 done
 for r in $(seq 1 ${ROUNDS:-2}); do
   for v in $VARIANTS; do
-    WEBPGPU_LIB=${v#*=} TAILN=0 step bench_${v%%=*}$r 300 python bench.py --steps ${STEPS:-20} --warmup 5 --no-cpu-baseline
+    WEBPGPU_LIB=${v#*=} TAILN=0 step bench_${v%%=*}$r 300 python bench.py --full --steps ${STEPS:-20} --warmup 5 --no-cpu-baseline
   done
 done
 for r in $(seq 1 ${ROUNDS:-2}); do

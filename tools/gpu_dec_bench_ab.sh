@@ -7,7 +7,7 @@ step decb_tests 400 python -u -m pytest tests/test_c3_real.py tests/test_gpu_fra
 for r in 1 2; do
   for v in default $B; do
     lib=webp_amd/libwebpgpu.so; [ $v != default ] && lib=webp_amd/libwebpgpu_$v.so
-    WEBPGPU_LIB=$lib TAILN=0 step decb_${v}_$r 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-c3c5
+    WEBPGPU_LIB=$lib TAILN=0 step decb_${v}_$r 300 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-c3c5
     echo "$r $v $(tail -1 gpurun_out/decb_${v}_$r.log | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); r=d["runs"]; print(d["value"], r["encode+decode"]["median"], r["decode"]["median"], d["stage_ms_isolated"]["decode"])')"
   done
 done

@@ -5,7 +5,7 @@
 source tools/gpu_step.sh
 OUT=gpurun_out/dectraffic
 mkdir -p $OUT
-B="--steps 3 --warmup 1 --runs 0 --iso-steps 1 --no-cpu-baseline --no-gather"
+B="--full --steps 3 --warmup 1 --runs 0 --iso-steps 1 --no-cpu-baseline --no-gather"
 step dt_bw 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/bw -o run -- python3 bench.py $B
 step dt_bf 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/bf -o run -- python3 bench.py $B
 step dt_cw 300 env C3_ONLY=1 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/cw -o run -- python3 tools/bench_c3.py

@@ -12,5 +12,5 @@ for i in 1 2; do
     echo "$i $v $(grep -h 'C3 real\|decode 16x' gpurun_out/c3ab_${v}_$i.log | sed 's/.*reconstruct+filter \([0-9.]*\) ms.*/\1/' | tr '\n' ' ')"
   done
 done
-TAILN=1 step bench_short 400 python bench.py --steps 10 --warmup 3 --no-cpu-baseline
+TAILN=1 step bench_short 400 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline
 python3 -c "import json; d=json.loads(open('gpurun_out/bench_short.log').read().strip().splitlines()[-1]); r=d['runs']; print(d['value'], r['encode+decode']['median'], r['encode']['median'], d['stage_ms_isolated']['encode'], d.get('c3'))"

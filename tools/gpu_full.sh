@@ -15,7 +15,7 @@ step() {  # name, limit, command...
 if [ "${PART:-a}" != b ]; then
 step gpu 900 python -u -m pytest tests -x -q -m gpu --timeout 300 --timeout-method thread
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
-TAILN=1 step bench 600 python bench.py --steps 10 --warmup 3
+TAILN=1 step bench 600 python bench.py --full --steps 10 --warmup 3
 TAILN=4 step c3 300 python tools/bench_c3.py
 TAILN=1 step c5 300 python tools/bench_c5.py
 TAILN=1 step aux 300 python tools/bench_aux.py

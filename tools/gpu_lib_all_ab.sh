@@ -11,7 +11,7 @@ for r in 1 2; do
     WEBPGPU_LIB=$lib TAILN=0 step all_c5_${v}_$r 200 python3 tools/bench_c5.py
     WEBPGPU_LIB=$lib TAILN=0 step all_c3_${v}_$r 200 python3 tools/bench_c3.py
     WEBPGPU_LIB=$lib TAILN=0 step all_aux_${v}_$r 200 python3 tools/bench_aux.py
-    WEBPGPU_LIB=$lib TAILN=0 step all_enc_${v}_$r 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-c3c5
+    WEBPGPU_LIB=$lib TAILN=0 step all_enc_${v}_$r 300 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-c3c5
     python3 - $v $r <<'PY'
 import json, sys
 v, r = sys.argv[1], sys.argv[2]

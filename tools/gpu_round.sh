@@ -5,7 +5,7 @@
 # ends the call.
 source tools/gpu_step.sh
 step suite 600 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread
-step bench 420 python bench.py
+step bench 420 python bench.py --full
 [ "${PROFILE:-1}" = 1 ] || exit 0
 step profile 1000 bash tools/profile.sh
 bash tools/gpu_enc_pmc.sh

@@ -5,7 +5,7 @@ set -e
 export TMPDIR=/tmp
 OUT=gpurun_out/prof
 mkdir -p $OUT
-ARGS="--steps ${STEPS:-5} --warmup 2 --no-cpu-baseline ${EXTRA:-}"
+ARGS="--full --steps ${STEPS:-5} --warmup 2 --no-cpu-baseline ${EXTRA:-}"
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- python3 bench.py $ARGS > $OUT/trace.log 2>&1
 # isolated launches (one batch at a time, as the bench line's stage_ms_isolated /
 # roofline.achieved time them): AverageNs of k_encode_rows is the roofline's launch

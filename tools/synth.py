@@ -53,12 +53,11 @@ def test_color_rgba():
     global _PHOTO
     if _PHOTO is None:
         import io
-        import os
 
         from PIL import Image
-        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden",
-                            "test_color_png.npz")
-        png = np.load(path)["png"].tobytes()
+
+        from tools import golden
+        png = golden.load("test_color_png.npz")["png"].tobytes()
         _PHOTO = np.ascontiguousarray(np.array(Image.open(io.BytesIO(png)).convert("RGBA")))
     return _PHOTO
 
