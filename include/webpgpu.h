@@ -25,9 +25,12 @@
  *    stalled a persistent kernel already running on another queue past that
  *    bound.  A timeout is reported once, by the first *_status call of that
  *    kernel family on the device after it; later clean launches report WG_OK.
- *  - Device state (timeout records, the encoder's constant tables) belongs
- *    to the device of `stream`; the frame entry points require it to be the
- *    calling thread's current device.
+ *  - Device state (timeout records, resident tables, launch configuration)
+ *    belongs to the device of `stream`.  The frame entry points that use it
+ *    -- wg_encode_mbs, wg_decode_frames, wg_sharpyuv_convert(_ex) with
+ *    sharpening, wg_vp8l_residual_image(_rows) and the gradient
+ *    wg_alpha_unfilter -- require that device to be the calling thread's
+ *    current device and return WG_EINVAL otherwise.
  *
  * The Go-side binding a maintainer adds (cgo) is shown in INTEGRATION.md.
  */

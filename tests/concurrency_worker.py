@@ -5,14 +5,23 @@ mode "race": the ABI used the way the reference is used concurrently
 (race_test.go:33 TestConcurrentEncodeDeterminism, :137-193 the concurrent
 encode / decode races; SURVEY 8(b): <= 6 row workers call the functions at
 once).  Six host threads, each with its own HIP stream, make the process's
-FIRST library calls at the same moment -- so the encoder's one-time constant
-table upload (encode_rd.hip g_tables_mu), the decoder's launch configuration,
-the gamma tables (wg_yuv.h call_once) and the device's timeout record
-(runtime.hip diag_words) are all initialised under the race -- and repeat
-them: wg_encode_mbs (through encode_frames: import -> analysis -> segments ->
-row order -> Phase A, status checked), wg_decode_frames (+ status) and
-wg_upsample_nrgba.  Afterwards the same jobs run serially on the default
-stream; every output must be byte-identical to its serial run.
+FIRST library calls at the same moment -- so the per-device records of the
+library (wg_device.h PerDevice: the encoder's one-time constant table upload
+in wg_encode_mbs, the decoder's launch configuration of decode.hip
+dec_config, the CU count and the device's timeout record of runtime.hip
+diag_words) and the gamma tables (wg_yuv.h call_once) are all initialised
+under the race -- and repeat them: wg_encode_mbs (through encode_frames:
+import -> analysis -> segments -> row order -> Phase A, status checked),
+wg_decode_frames (+ status) and wg_upsample_nrgba.  Afterwards the same jobs
+run serially on the default stream; every output must be byte-identical to
+its serial run.
+
+mode "tables": the same race over the two one-time uploads "race" does not
+reach.  Every thread calls frames.sharpyuv_convert on one 64x48 RGB image,
+with transfer 13 on half the threads and 1 on the others (two table slots of
+one device's record, sharpyuv_host.cpp sharpyuv_tables_device), and
+lossless.ResidualImage on one 64x40 image at bits 3 (the slog2 table,
+vp8l_host.cpp vp8l_slog2_lut_device).
 
 mode "diag": the *_status report of a timed-out wait: an
 injected timeout is reported by the next status call of its kernel family
@@ -82,13 +91,26 @@ def job_upsample(k):
     return run
 
 
-JOBS = [job_encode, job_decode, job_upsample]
+def job_tables(k):
+    from webp_amd import frames, lossless
+    r = np.random.default_rng(200 + k)
+    rgb = torch.from_numpy(r.integers(0, 256, (1, 48, 64, 3), dtype=np.uint8)).cuda()
+    argb = torch.from_numpy(r.integers(-2**31, 2**31, (40, 64), dtype=np.int64).astype(np.int32)).cuda()
+    transfer = 13 if k % 2 == 0 else 1  # sRGB / BT.709: two table slots
+
+    def run():
+        return list(frames.sharpyuv_convert(rgb, transfer=transfer)) + list(lossless.ResidualImage(argb, 3, 75))
+    return run
 
 
-def race():
+JOBS = {"race": [job_encode, job_decode, job_upsample], "tables": [job_tables]}
+
+
+def race(mode="race"):
     # inputs are made (and moved to the device) before any library call; the
     # threads' first calls into libwebpgpu.so happen together at the barrier
-    runs = [JOBS[k % 3](k) for k in range(THREADS)]
+    jobs = JOBS[mode]
+    runs = [jobs[k % len(jobs)](k) for k in range(THREADS)]
     torch.cuda.synchronize()
     start = threading.Barrier(THREADS)
     results, errors = [None] * THREADS, []
@@ -122,7 +144,7 @@ def race():
                     if a.shape != b.shape or not np.array_equal(a, b):
                         mismatches.append((k, rep, j))
     ok = not errors and not mismatches
-    print(json.dumps({"mode": "race", "ok": ok, "threads": THREADS, "repeats": REPEATS, "errors": errors,
+    print(json.dumps({"mode": mode, "ok": ok, "threads": THREADS, "repeats": REPEATS, "errors": errors,
                       "mismatches": mismatches}), flush=True)
     return ok
 
@@ -161,4 +183,4 @@ def diag():
 
 if __name__ == "__main__":
     mode = sys.argv[1] if len(sys.argv) > 1 else "race"
-    sys.exit(0 if (race() if mode == "race" else diag()) else 1)
+    sys.exit(0 if (diag() if mode == "diag" else race(mode)) else 1)

@@ -4,7 +4,7 @@ six host threads with their own streams make a fresh process's first library
 calls at once (the one-time table uploads race) and repeat them; outputs
 must be byte-identical to a serial run.  And the timeout report of the
 persistent kernels: reported once, then clean launches succeed again
-(ADVICE r03).  Both run in a fresh child process (tests/concurrency_worker.py)
+(ADVICE r03).  Each runs in a fresh child process (tests/concurrency_worker.py)
 so that no earlier test has initialised the library's process-wide state."""
 import json
 import os
@@ -29,6 +29,14 @@ def run_worker(mode):
 def test_gpu_concurrent_callers_are_deterministic(cuda):
     rep = run_worker("race")
     assert rep["threads"] == 6 and not rep["mismatches"]
+
+
+@pytest.mark.gpu
+def test_gpu_concurrent_first_table_uploads_are_deterministic(cuda):
+    """The SharpYUV gamma tables (two transfer functions, so two slots of one
+    device's record) and the VP8L slog2 table, first made under the same race."""
+    rep = run_worker("tables")
+    assert rep["threads"] == 6 and not rep["mismatches"] and not rep["errors"]
 
 
 @pytest.mark.gpu

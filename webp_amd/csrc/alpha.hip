@@ -211,12 +211,12 @@ __global__ __launch_bounds__(1024) void k_alpha_vseg(uint8_t* data, int w, int h
 struct GArgs {
   uint8_t* data;
   int* ctl;       // [0] band dequeue, [1] error
-  int* diag;      // wg::diag_words + DIAG_ALPHA
+  int* diag;      // wg::diag_words(s, DIAG_ALPHA)
   int* progress;  // [n_img][bands]
   int64_t pitch;
   int w, h, bands, n_img;
 };
-constexpr uint64_t SPIN_TICKS = 200000000ull;  // 2 s of s_memrealtime
+using wg::SPIN_TICKS;  // the bound of every wait below (wg_common.h)
 
 // gradient unfilter below row 0 (row 0 already scanned).  Rows 1.. are cut
 // into bands of 64; band b holds rows 1 + 64b .. 64 + 64b, one wave each.
@@ -398,7 +398,7 @@ constexpr int GD_CH = 16;  // steps per chunk
 struct GdArgs {
   uint8_t* data;
   int* ctl;        // [0] band dequeue, [1] error
-  int* diag;       // wg::diag_words + DIAG_ALPHA
+  int* diag;       // wg::diag_words(s, DIAG_ALPHA)
   uint64_t* hand;  // [n_img][bands + 1][w / 4] granules {4 pixels, tag}: row 0, then each band's last row
   int64_t pitch;
   int w, h, bands, n_img;
@@ -959,11 +959,12 @@ extern "C" int wg_alpha_unfilter(int32_t filter, uint8_t* data, int32_t width, i
   }
   WG_REQUIRE(work);
   WG_REQUIRE((reinterpret_cast<uintptr_t>(work) & 15) == 0);
+  int dev = 0;  // (the persistent kernels' grid is sized by this device's CUs)
+  if (const int e = wg::call_device(s, "wg_alpha_unfilter", &dev)) return e;
+  const int cus = wg::device_cus(dev);
+  if (cus <= 0) return WG_EHIP;
   if (hipMemsetAsync(work, 0, wg_alpha_unfilter_work_bytes(width, height, n_images), s) != hipSuccess)
     return wg::check_launch("hipMemsetAsync(alpha work)");
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-    return wg::check_launch("device query");
   const int bands = (height - 1 + 63) / 64;
   const int total = bands * n_images;
   const int grid = total < 4 * cus ? total : 4 * cus;
@@ -972,9 +973,8 @@ extern "C" int wg_alpha_unfilter(int32_t filter, uint8_t* data, int32_t width, i
     GdArgs g;
     g.data = data;
     g.ctl = static_cast<int*>(work);
-    g.diag = wg::diag_words(s);
+    g.diag = wg::diag_words(s, wg::DIAG_ALPHA);
     if (!g.diag) return WG_EHIP;
-    g.diag += wg::DIAG_ALPHA;
     g.hand = reinterpret_cast<uint64_t*>(static_cast<uint8_t*>(work) + gd_hand_offset(height, n_images));
     g.pitch = pitch;
     g.w = width;
@@ -989,9 +989,8 @@ extern "C" int wg_alpha_unfilter(int32_t filter, uint8_t* data, int32_t width, i
   GArgs a;
   a.data = data;
   a.ctl = static_cast<int*>(work);
-  a.diag = wg::diag_words(s);
+  a.diag = wg::diag_words(s, wg::DIAG_ALPHA);
   if (!a.diag) return WG_EHIP;
-  a.diag += wg::DIAG_ALPHA;
   a.progress = a.ctl + 4;
   a.pitch = pitch;
   a.w = width;

@@ -26,8 +26,6 @@
 #include <cstdlib>
 #include <cstring>
 
-#include <mutex>
-
 #include "wg_common.h"
 #include "wg_dsp.h"
 #include "wg_instr.h"
@@ -119,7 +117,7 @@ struct DecArgs {
   uint8_t* bot;   // [n_img][mbw][BOT_BYTES] (k_decode_split): final rows 12..15 of a band's last row, for the next band
   int* progress;  // [n_img][mbh]: macroblocks completed (reconstructed + filtered + stored)
   int* ctl;       // [0] row dequeue counter, [1] error flag (wait timeout)
-  int* diag;      // wg::diag_words + DIAG_DECODE
+  int* diag;      // wg::diag_words(s, DIAG_DECODE)
   int filter_type, mbw, mbh, n_img;
 };
 
@@ -208,7 +206,7 @@ __device__ __forceinline__ int opaque_lane() {
   return l;
 }
 
-constexpr uint64_t SPIN_TICKS = 200000000ull;  // 2 s of the 100 MHz s_memrealtime clock per wait
+using wg::SPIN_TICKS;  // the bound of every wait below (wg_common.h)
 
 // Rows per workgroup (one wave each) and the depth of the intra-band LDS rings.
 constexpr int DW = 4;
@@ -1412,8 +1410,8 @@ __global__ __launch_bounds__(128 * SW) void k_decode_split(DecArgs a) {
   STAMP_FLUSH();
 }
 
-// launch configuration, read once per process (under the mutex: host
-// threads may call wg_decode_frames concurrently)
+// launch configuration, made once per device (host threads may call
+// wg_decode_frames concurrently); the WG_DECODE_* knobs are read once
 struct DecConfig {
   int num_cus = 0;
   int rows_per_cu = 0;   // resident k_decode_bands workgroups per CU (occupancy)
@@ -1421,29 +1419,32 @@ struct DecConfig {
   int max_wg = 0;        // grid cap (0: every resident slot; WG_DECODE_MAX_WG)
   int force = 0;         // WG_DECODE_KERNEL=split / bands forces one kernel (A/B); 0: by batch size
 };
-std::mutex g_dec_cfg_mu;
-DecConfig g_dec_cfg;
 
-int dec_config(DecConfig* out) {
-  std::lock_guard<std::mutex> lock(g_dec_cfg_mu);
-  DecConfig& c = g_dec_cfg;
-  if (c.num_cus == 0) {
-    int dev = 0, cus = 0, per_cu = 0, per_cu_s = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0 ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_decode_bands, 64 * DW, 0) != hipSuccess || per_cu <= 0 ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_s, k_decode_split, 128 * SW, 0) != hipSuccess ||
-        per_cu_s <= 0)
-      return wg::check_launch("decode occupancy query");
-    c.rows_per_cu = per_cu;
-    c.split_per_cu = per_cu_s;
-    if (const char* e = getenv("WG_DECODE_WG_PER_CU")) c.rows_per_cu = atoi(e) > 0 ? atoi(e) : per_cu;  // tuning
+// dev is the calling thread's current device (the occupancy queries answer
+// for that one); nullptr (error set) if they fail
+const DecConfig* dec_config(int dev) {
+  static const DecConfig env = [] {  // rows_per_cu 0: the occupancy
+    DecConfig c;
+    if (const char* e = getenv("WG_DECODE_WG_PER_CU")) c.rows_per_cu = atoi(e) > 0 ? atoi(e) : 0;  // tuning
     if (const char* e = getenv("WG_DECODE_KERNEL")) c.force = strcmp(e, "bands") == 0 ? 2 : (strcmp(e, "split") == 0 ? 1 : 0);
     if (const char* e = getenv("WG_DECODE_MAX_WG")) c.max_wg = atoi(e) > 0 ? atoi(e) : 0;  // tuning: cap the grid
-    c.num_cus = cus;
-  }
-  *out = c;
-  return WG_OK;
+    return c;
+  }();
+  static wg::PerDevice<DecConfig> configs;
+  const DecConfig* cfg = configs.get(dev, [&](DecConfig& c) {
+    int per_cu = 0;
+    c = env;
+    c.num_cus = wg::device_cus(dev);
+    if (c.num_cus <= 0 ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_decode_bands, 64 * DW, 0) != hipSuccess || per_cu <= 0 ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&c.split_per_cu, k_decode_split, 128 * SW, 0) != hipSuccess ||
+        c.split_per_cu <= 0)
+      return false;
+    if (c.rows_per_cu == 0) c.rows_per_cu = per_cu;
+    return true;
+  });
+  if (!cfg) (void)wg::check_launch("decode occupancy query");
+  return cfg;
 }
 
 // the switch between the two kernels (see wg_decode_frames)
@@ -1493,11 +1494,12 @@ extern "C" int wg_decode_frames(const wg_mb_info* mb, const int16_t* coeffs, int
   a.mbh = mbh;
   a.n_img = n_images;
   hipStream_t s = wg::as_stream(stream);
-  a.diag = wg::diag_words(s);
+  int dev = 0;
+  if (const int rc = wg::call_device(s, "wg_decode_frames", &dev)) return rc;
+  a.diag = wg::diag_words(s, wg::DIAG_DECODE);
   if (!a.diag) return WG_EHIP;
-  a.diag += wg::DIAG_DECODE;
-  DecConfig cfg;
-  if (const int e = dec_config(&cfg)) return e;
+  const DecConfig* cfg = dec_config(dev);
+  if (!cfg) return WG_EHIP;
   if (hipMemsetAsync(a.ctl, 0, sizeof(int) * (2 * (size_t)n_images * mbh + 4), s) != hipSuccess)
     return wg::check_launch("hipMemsetAsync(decode ctl)");
   // k_decode_split (two waves a row: reconstruction and loop filter apart)
@@ -1510,24 +1512,25 @@ extern "C" int wg_decode_frames(const wg_mb_info* mb, const int16_t* coeffs, int
   // 1080p: whole-path median 6,495 -> 7,065 MPix/s, decode side alone 77.4k
   // -> 76.1k).  The switch is at twice the rows of the resident
   // split workgroups (a heuristic between those two measured points).
-  if (use_split(cfg, mbh, n_images)) {
+  if (use_split(*cfg, mbh, n_images)) {
     const int bands = n_images * ((mbh + SW - 1) / SW);
-    int grid = bands < cfg.split_per_cu * cfg.num_cus ? bands : cfg.split_per_cu * cfg.num_cus;
-    if (cfg.max_wg > 0 && grid > cfg.max_wg) grid = cfg.max_wg;
+    int grid = bands < cfg->split_per_cu * cfg->num_cus ? bands : cfg->split_per_cu * cfg->num_cus;
+    if (cfg->max_wg > 0 && grid > cfg->max_wg) grid = cfg->max_wg;
     hipLaunchKernelGGL(k_decode_split, dim3((unsigned)grid), dim3(128 * SW), 0, s, a);
     return wg::check_launch("k_decode_split");
   }
   const int bands = n_images * ((mbh + DW - 1) / DW);
-  const int grid = bands < cfg.rows_per_cu * cfg.num_cus ? bands : cfg.rows_per_cu * cfg.num_cus;
+  const int grid = bands < cfg->rows_per_cu * cfg->num_cus ? bands : cfg->rows_per_cu * cfg->num_cus;
   hipLaunchKernelGGL(k_decode_bands, dim3((unsigned)grid), dim3(64 * DW), 0, s, a);
   return wg::check_launch("k_decode_bands");
 }
 
 extern "C" int wg_decode_kernel(int32_t mbh, int32_t n_images) {
   WG_REQUIRE(mbh > 0 && n_images > 0);
-  DecConfig cfg;
-  if (const int e = dec_config(&cfg)) return e;
-  return use_split(cfg, mbh, n_images) ? 1 : 2;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return wg::check_launch("hipGetDevice");
+  const DecConfig* cfg = dec_config(dev);
+  return !cfg ? WG_EHIP : use_split(*cfg, mbh, n_images) ? 1 : 2;
 }
 
 extern "C" int wg_decode_status(const void* work, int32_t mbw, int32_t n_images, void* stream) {

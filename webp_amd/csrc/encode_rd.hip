@@ -41,7 +41,6 @@
 //              reconstruction and export
 // All integer; bit-exact with the C restatement (oracle/lossy_rd.c).
 #include <cstdlib>
-#include <mutex>
 
 #include "vp8_tables.h"
 #include "wg_common.h"
@@ -1214,7 +1213,7 @@ struct EncArgs {
   MbEnc* out;
   uint8_t* top;   // [n_img][mbw][REC]
   int* ctl;       // [0] dequeue, [1] error
-  int* diag;      // wg::diag_words + DIAG_ENCODE
+  int* diag;      // wg::diag_words(s, DIAG_ENCODE)
   const int* order;  // the work buffer's row schedule (wg_encode_row_order): dequeue index -> row * n_img + image
   const int* border; // the same schedule over bands of WAVES rows: dequeue index -> band * n_img + image
   const int* order_tag;  // {ORDER_TAG ^ n_img, ~(ORDER_TAG ^ mbh)} when the schedule was built for this batch shape, else (row, image) order
@@ -1222,7 +1221,7 @@ struct EncArgs {
   int width, height, mbw, mbh, n_img, quality;
 };
 
-constexpr uint64_t SPIN_TICKS = 200000000ull;
+using wg::SPIN_TICKS;  // the bound of every wait below (wg_common.h)
 
 constexpr int ORDER_TAG = 0x5e0d0000;  // marks a row schedule in the work buffer (xor the batch shape)
 
@@ -2636,11 +2635,6 @@ __global__ __launch_bounds__(64 * (PAIR ? 2 : WAVES * GROUPS), PAIR ? 2 : 2) voi
   ESTAMP_FLUSH();
 }
 
-// Devices whose constant tables are uploaded: one bit per device, set under
-// the mutex so host threads driving different devices do not race.
-std::mutex g_tables_mu;
-uint64_t g_tables_ready_mask = 0;
-
 // VP8FixedCostsI4[top][left][mode] (computeFixedCostsI4,
 // internal/lossy/encode_analysis.go:1498-1520): the mode tree walked with the
 // VP8 bmode probabilities (i4ModeCost :1511).
@@ -2810,25 +2804,20 @@ extern "C" int wg_encode_mbs(const uint8_t* y, const uint8_t* u, const uint8_t* 
   WG_REQUIRE(y_pitch >= (int64_t)256 * mbw * mbh && uv_pitch >= (int64_t)64 * mbw * mbh && (y_pitch & 15) == 0 &&
              (uv_pitch & 7) == 0);
   hipStream_t s = wg::as_stream(stream);
-  int dev = 0, sdev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return wg::check_launch("hipGetDevice");
-  if (wg::stream_device(s, &sdev) != WG_OK) return WG_EHIP;
-  WG_REQUIRE(dev >= 0 && dev < 64);
   // the constant tables are uploaded to, and the occupancy read from, the
   // current device: the stream must be on it (webpgpu.h conventions)
-  if (sdev != dev) return wg::invalid("wg_encode_mbs: the stream's device is not the current device");
-  {
-    std::lock_guard<std::mutex> lock(g_tables_mu);
-    if (!(g_tables_ready_mask >> dev & 1)) {  // constant tables: level codes, fixed I4 mode costs, scan orders
-      uint16_t fixed[1000];
-      build_fixed_costs_i4(fixed);
-      if (hipMemcpyToSymbol(HIP_SYMBOL(c_fixed_i4), fixed, sizeof(fixed)) != hipSuccess ||
-          hipMemcpyToSymbol(HIP_SYMBOL(c_level_codes), vp8_level_codes, sizeof(vp8_level_codes)) != hipSuccess ||
-          hipMemcpyToSymbol(HIP_SYMBOL(c_wtrellis), vp8_weight_trellis, sizeof(vp8_weight_trellis)) != hipSuccess)
-        return wg::check_launch("encode tables");
-      g_tables_ready_mask |= 1ull << dev;
-    }
-  }
+  int dev = 0;
+  if (const int rc = wg::call_device(s, "wg_encode_mbs", &dev)) return rc;
+  // constant tables: level codes, fixed I4 mode costs, scan orders
+  static wg::PerDevice<bool> tables;
+  if (!tables.get(dev, [](bool& up) {
+        uint16_t fixed[1000];
+        build_fixed_costs_i4(fixed);
+        return up = hipMemcpyToSymbol(HIP_SYMBOL(c_fixed_i4), fixed, sizeof(fixed)) == hipSuccess &&
+                    hipMemcpyToSymbol(HIP_SYMBOL(c_level_codes), vp8_level_codes, sizeof(vp8_level_codes)) == hipSuccess &&
+                    hipMemcpyToSymbol(HIP_SYMBOL(c_wtrellis), vp8_weight_trellis, sizeof(vp8_weight_trellis)) == hipSuccess;
+      }))
+    return wg::check_launch("encode tables");
   EncArgs a;
   a.y = y;
   a.u = u;
@@ -2854,15 +2843,15 @@ extern "C" int wg_encode_mbs(const uint8_t* y, const uint8_t* u, const uint8_t* 
   a.order = a.ctl + 8;  // work: records | ctl[4] | tag[4] | order | slack | border
   a.order_tag = a.order - 4;
   a.border = a.order + (size_t)n_images * mbh + n_images;
-  a.diag = wg::diag_words(s);
+  a.diag = wg::diag_words(s, wg::DIAG_ENCODE);
   if (!a.diag) return WG_EHIP;
-  a.diag += wg::DIAG_ENCODE;
   // the hand-off records (every tag 0: no row has written), the control words
   // and the progress words, cleared for this launch
   if (hipMemsetAsync(a.top, 0, (size_t)n_images * mbw * REC + sizeof(int) * 4, s) != hipSuccess)
     return wg::check_launch("hipMemsetAsync(encode records + ctl)");
-  int cus = 0, per_cu = 0, per_cu_pair = 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+  const int cus = wg::device_cus(dev);
+  int per_cu = 0, per_cu_pair = 0;
+  if (cus <= 0 ||
       hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_encode_rows<true, false>, 64 * WAVES * GROUPS, 0) != hipSuccess ||
       hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_pair, k_encode_rows<true, true>, 128, 0) != hipSuccess ||
       per_cu <= 0 || per_cu_pair <= 0)

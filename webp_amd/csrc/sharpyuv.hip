@@ -150,7 +150,7 @@ __global__ __launch_bounds__(256) void k_sharp_init(SharpArgs a, int n_img) {
   }
 }
 
-constexpr uint64_t SPIN_TICKS = 200000000ull;  // 2 s of s_memrealtime (100 MHz)
+using wg::SPIN_TICKS;  // the bound of every wait below (wg_common.h)
 
 // Hand-off loads / stores between the iteration workgroups: agent-scope
 // relaxed atomics, i.e. sc1 (write-through stores, L1-bypassing loads); every
@@ -713,7 +713,7 @@ __global__ __launch_bounds__(256) void k_sharp_standard(StdArgs a, int n_img) {
 namespace wg {
 // sharpyuv_host.cpp: g2l[1026] then l2g[514] (uint32), then for tf != sRGB
 // the direct LinearToGamma table (uint16, *lut_n entries)
-const void* sharpyuv_tables_device(int tf, int* lut_n);
+const void* sharpyuv_tables_device(int dev, int tf, int* lut_n);
 }
 
 namespace {
@@ -789,8 +789,9 @@ extern "C" int wg_sharpyuv_convert_ex(const uint8_t* rgb, int32_t width, int32_t
   const int w = (width + 1) & ~1, h = (height + 1) & ~1;
   const int uvw = w / 2, uvh = h / 2;
   const int nb = sharp_bands(width);
-  int lut_n = 0;
-  const void* tabs = wg::sharpyuv_tables_device(transfer, &lut_n);
+  int dev = 0, lut_n = 0;  // (the tables and the resident-workgroup bound below are this device's)
+  if (const int rc = wg::call_device(s, "wg_sharpyuv_convert_ex", &dev)) return rc;
+  const void* tabs = wg::sharpyuv_tables_device(dev, transfer, &lut_n);
   if (!tabs) return WG_EHIP;
   const bool lut = transfer != 13;
   const SharpLayout L = sharp_layout(width, height);
@@ -842,8 +843,9 @@ extern "C" int wg_sharpyuv_convert_ex(const uint8_t* rgb, int32_t width, int32_t
   if (rc != WG_OK) return rc;
   // every wait is on a block of the same launch: launch at most as many
   // images as the device holds at once (4 iterations x nb bands each)
-  int dev = 0, cus = 0, per_cu = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+  const int cus = wg::device_cus(dev);
+  int per_cu = 0;
+  if (cus <= 0 ||
       hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_sharp_wave<false>, 128, 0) != hipSuccess ||
       per_cu <= 0)
     return wg::check_launch("sharpyuv occupancy");

@@ -19,16 +19,18 @@
 #include <math.h>
 
 #include <algorithm>
-#include <mutex>
 
 #include "wg_common_host.h"
+#include "wg_device.h"
 
 namespace {
 
-constexpr int kG2L = 1026, kL2G = 514, kMaxDev = 64, kMaxTf = 19;
-std::mutex g_mu;
-void* g_tabs[kMaxDev][kMaxTf] = {{nullptr}};
-int g_lut_n[kMaxDev][kMaxTf] = {{0}};
+constexpr int kG2L = 1026, kL2G = 514, kMaxTf = 19;
+struct DeviceTabs {  // one device's resident tables, by transfer function
+  void* tabs[kMaxTf];
+  int lut_n[kMaxTf];
+};
+wg::PerDevice<DeviceTabs> g_tabs;
 
 float powf_go(float b, float e) { return (float)pow((double)b, (double)e); }
 float clampf(float x, float lo, float hi) { return x < lo ? lo : (x > hi ? hi : x); }
@@ -154,42 +156,45 @@ void build(uint32_t* g2l, uint32_t* l2g) {
   l2g[513] = l2g[512];
 }
 
+// builds and uploads tf's tables to the current device; nullptr on failure
+void* upload_tables(int tf, int* lut_n) {
+  std::vector<uint32_t> h(kG2L + kL2G, 0u);
+  std::vector<uint16_t> lut;
+  if (tf == 13)
+    build(h.data(), h.data() + kG2L);
+  else
+    build_tf(tf, h.data(), lut);
+  const size_t bytes = sizeof(uint32_t) * h.size() + sizeof(uint16_t) * lut.size();
+  void* d = nullptr;
+  if (hipMalloc(&d, bytes) != hipSuccess ||
+      hipMemcpy(d, h.data(), sizeof(uint32_t) * h.size(), hipMemcpyHostToDevice) != hipSuccess ||
+      (!lut.empty() && hipMemcpy(static_cast<uint8_t*>(d) + sizeof(uint32_t) * h.size(), lut.data(),
+                                 sizeof(uint16_t) * lut.size(), hipMemcpyHostToDevice) != hipSuccess)) {
+    if (d) (void)hipFree(d);
+    return nullptr;
+  }
+  *lut_n = (int)lut.size();
+  return d;
+}
+
 }  // namespace
 
 namespace wg {
 
-// Device tables for transfer function tf: g2l[1026] + l2g[514] (uint32) and,
-// for tf != sRGB, the direct LinearToGamma table (uint16) right after them;
-// *lut_n = its length (0 for sRGB).
-const void* sharpyuv_tables_device(int tf, int* lut_n) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev || tf < 0 || tf >= kMaxTf) {
-    set_error("sharpyuv: hipGetDevice failed or bad transfer function");
-    return nullptr;
-  }
-  std::lock_guard<std::mutex> lock(g_mu);
-  if (!g_tabs[dev][tf]) {
-    std::vector<uint32_t> h(kG2L + kL2G, 0u);
-    std::vector<uint16_t> lut;
-    if (tf == 13)
-      build(h.data(), h.data() + kG2L);
-    else
-      build_tf(tf, h.data(), lut);
-    const size_t bytes = sizeof(uint32_t) * h.size() + sizeof(uint16_t) * lut.size();
-    void* d = nullptr;
-    if (hipMalloc(&d, bytes) != hipSuccess ||
-        hipMemcpy(d, h.data(), sizeof(uint32_t) * h.size(), hipMemcpyHostToDevice) != hipSuccess ||
-        (!lut.empty() && hipMemcpy(static_cast<uint8_t*>(d) + sizeof(uint32_t) * h.size(), lut.data(),
-                                   sizeof(uint16_t) * lut.size(), hipMemcpyHostToDevice) != hipSuccess)) {
-      set_error("sharpyuv: cannot upload the gamma tables");
-      if (d) (void)hipFree(d);
-      return nullptr;
-    }
-    g_tabs[dev][tf] = d;
-    g_lut_n[dev][tf] = (int)lut.size();
-  }
-  *lut_n = g_lut_n[dev][tf];
-  return g_tabs[dev][tf];
+// Device tables for transfer function tf on device dev (the calling thread's
+// current device): g2l[1026] + l2g[514] (uint32) and, for tf != sRGB, the
+// direct LinearToGamma table (uint16) right after them; *lut_n = its length
+// (0 for sRGB).
+const void* sharpyuv_tables_device(int dev, int tf, int* lut_n) {
+  const void* tabs = nullptr;
+  if (tf >= 0 && tf < kMaxTf)
+    g_tabs.update(dev, [&](DeviceTabs& t) {
+      if (!t.tabs[tf]) t.tabs[tf] = upload_tables(tf, &t.lut_n[tf]);
+      tabs = t.tabs[tf];
+      *lut_n = t.lut_n[tf];
+    });
+  if (!tabs) set_error("sharpyuv: cannot upload the gamma tables (or bad device / transfer function)");
+  return tabs;
 }
 
 }  // namespace wg

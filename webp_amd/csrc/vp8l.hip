@@ -520,14 +520,14 @@ struct InvArgs {
   const uint32_t* in;
   uint32_t* out;
   int* ctl;        // [0] band dequeue counter, [1] error flag (wait timeout)
-  int* diag;       // wg::diag_words + DIAG_VP8L_INVERSE
+  int* diag;       // wg::diag_words(s, DIAG_VP8L_INVERSE)
   uint64_t* hand;  // [n_img][bands][width] {pixel, tag} granules of each band's last row
   uint64_t* stamps;  // (WG_TIMELINES builds) [band idx][4]: start, end, poll ticks | polls << 32, block
   int64_t pitch;
   int width, height, bits, tiles_x, tiles_y, bands, n_img;
 };
 
-constexpr uint64_t SPIN_TICKS = 200000000ull;  // 2 s of s_memrealtime
+using wg::SPIN_TICKS;  // the bound of every wait below (wg_common.h)
 
 // predictorInverseTransform.  Rows depend on the row above (T, TL, TR) and on
 // their own left neighbour.  A wave takes a band of 32 rows and walks it as a
@@ -902,7 +902,7 @@ int subsample(int size, int bits) { return (size + (1 << bits) - 1) >> bits; }
 }  // namespace
 
 namespace wg {
-const double* vp8l_slog2_lut_device();  // vp8l_host.cpp
+const double* vp8l_slog2_lut_device(int dev);  // vp8l_host.cpp
 }
 
 extern "C" int wg_vp8l_residual_image_rows(const uint32_t* argb, int32_t width, int32_t height, int64_t image_pitch,
@@ -913,9 +913,11 @@ extern "C" int wg_vp8l_residual_image_rows(const uint32_t* argb, int32_t width, 
   const int tiles_x = subsample(width, bits), tiles_y = subsample(height, bits);
   WG_REQUIRE(ty_begin >= 0 && ty_begin < ty_end && ty_end <= tiles_y);
   WG_REQUIRE(height <= 65535 && n_images <= 65535);  // (k_vp8l_residual's grid y / z)
-  const double* lut = wg::vp8l_slog2_lut_device();
-  if (!lut) return WG_EHIP;
   hipStream_t s = wg::as_stream(stream);
+  int dev = 0;
+  if (const int rc = wg::call_device(s, "wg_vp8l_residual_image_rows", &dev)) return rc;
+  const double* lut = wg::vp8l_slog2_lut_device(dev);
+  if (!lut) return WG_EHIP;
   SelArgs sa;
   sa.argb = argb;
   sa.pitch = image_pitch;
@@ -985,9 +987,8 @@ extern "C" int wg_vp8l_inverse_predictor(const uint32_t* modes, int32_t bits, in
   a.bands = (height + INV_ROWS - 1) / INV_ROWS;
   a.n_img = n_images;
   a.ctl = static_cast<int*>(work);
-  a.diag = wg::diag_words(s);
+  a.diag = wg::diag_words(s, wg::DIAG_VP8L_INVERSE);
   if (!a.diag) return WG_EHIP;
-  a.diag += wg::DIAG_VP8L_INVERSE;
   a.hand = reinterpret_cast<uint64_t*>(static_cast<uint8_t*>(work) + 16);
   a.stamps = a.hand + (size_t)n_images * a.bands * ((width + 1) & ~1);
   a.pitch = image_pitch;

@@ -8,10 +8,10 @@
 #include <hip/hip_runtime_api.h>
 #include <math.h>
 
-#include <mutex>
 #include <vector>
 
 #include "wg_common_host.h"
+#include "wg_device.h"
 
 namespace {
 
@@ -43,35 +43,29 @@ double go_log2(double x) {
 }
 
 constexpr int kLut = 65536;
-constexpr int kMaxDev = 64;
-std::mutex g_mu;
-double* g_lut[kMaxDev] = {nullptr};
+wg::PerDevice<double*> g_lut;
 
 }  // namespace
 
 namespace wg {
 
-const double* vp8l_slog2_lut_device() {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) {
-    set_error("vp8l: hipGetDevice failed");
-    return nullptr;
-  }
-  std::lock_guard<std::mutex> lock(g_mu);
-  if (!g_lut[dev]) {
+// (dev: the calling thread's current device, where the table is made)
+const double* vp8l_slog2_lut_device(int dev) {
+  double* const* lut = g_lut.get(dev, [](double*& out) {
     std::vector<double> h(kLut);
     h[0] = 0;
     for (int i = 1; i < kLut; i++) h[i] = (double)i * go_log2((double)i);
     void* d = nullptr;
     if (hipMalloc(&d, kLut * sizeof(double)) != hipSuccess ||
         hipMemcpy(d, h.data(), kLut * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
-      set_error("vp8l: cannot upload the slog2 table");
       if (d) (void)hipFree(d);
-      return nullptr;
+      return false;
     }
-    g_lut[dev] = static_cast<double*>(d);
-  }
-  return g_lut[dev];
+    out = static_cast<double*>(d);
+    return true;
+  });
+  if (!lut) set_error("vp8l: cannot upload the slog2 table");
+  return lut ? *lut : nullptr;
 }
 
 }  // namespace wg

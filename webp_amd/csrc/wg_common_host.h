@@ -1,5 +1,5 @@
-// wg_common_host.h -- error / argument helpers for host-only (no HIP) C-ABI
-// translation units; the same contract as wg_common.h.
+// wg_common_host.h -- error / argument helpers of every C-ABI translation
+// unit; all a host-only (no HIP) one needs.  wg_common.h adds the HIP side.
 #pragma once
 #include <stdint.h>
 
