@@ -28,8 +28,8 @@
  *  - Device state (timeout records, resident tables, launch configuration)
  *    belongs to the device of `stream`.  The frame entry points that use it
  *    -- wg_encode_mbs, wg_decode_frames, wg_sharpyuv_convert(_ex) with
- *    sharpening, wg_vp8l_residual_image(_rows) and the gradient
- *    wg_alpha_unfilter -- require that device to be the calling thread's
+ *    sharpening, wg_sharpyuv_import_rgba, wg_vp8l_residual_image(_rows) and
+ *    the gradient wg_alpha_unfilter -- require that device to be the calling thread's
  *    current device and return WG_EINVAL otherwise.
  *
  * The Go-side binding a maintainer adds (cgo) is shown in INTEGRATION.md.
@@ -386,6 +386,40 @@ int wg_decode_status(const void* work, int32_t mbw, int32_t n_images, void* stre
 int wg_import_rgba(const uint8_t* rgba, int32_t w, int32_t h, int32_t stride, int64_t rgba_pitch,
                    int32_t has_alpha, uint8_t* y, uint8_t* u, uint8_t* v, int64_t y_pitch, int64_t uv_pitch,
                    int32_t n_images, void* stream);
+
+/* VP8Encoder.importYCbCr (internal/lossy/encode.go:544-585): n 4:2:0 images
+ * (Y w x h at sy_stride / sy_pitch; U, V (w+1)/2 x (h+1)/2 at suv_stride /
+ * suv_pitch) into the encoder's padded planes (Y stride 16*mbw, 16*mbh rows;
+ * U/V stride 8*mbw, 8*mbh rows; y_pitch / uv_pitch per image), the last
+ * column and row replicated.  No minimum size (mbh >= 4 is wg_encode_mbs's
+ * rule).  Two modes:
+ *  - copy: source and destination do not overlap.  The source may have any
+ *    alignment and any stride >= w; the destination rules are those of
+ *    wg_import_rgba (y, u, v 4-byte aligned, y_pitch a multiple of 8,
+ *    uv_pitch of 4).  Every byte of the padded planes is written, nothing
+ *    outside [img * pitch, img * pitch + plane bytes).
+ *  - in place: sy == y, su == u, sv == v, sy_stride == 16*mbw, suv_stride ==
+ *    8*mbw, sy_pitch == y_pitch and suv_pitch == uv_pitch.  Only the margin
+ *    (columns >= w of rows < h, and all rows >= h; chroma likewise) is stored
+ *    to, from interior bytes: what a producer that wrote the w x h interior
+ *    of the padded planes itself (wg_sharpyuv_import_rgba) still needs.
+ * Any other overlap between the bytes the n source images span and the bytes
+ * the n destination images span is WG_EINVAL. */
+int wg_import_ycbcr(const uint8_t* sy, int32_t sy_stride, int64_t sy_pitch,
+                    const uint8_t* su, const uint8_t* sv, int32_t suv_stride, int64_t suv_pitch,
+                    int32_t w, int32_t h, uint8_t* y, uint8_t* u, uint8_t* v,
+                    int64_t y_pitch, int64_t uv_pitch, int32_t n_images, void* stream);
+
+/* webp.Encode's UseSharpYUV import: sharpYUVConvert (encode.go:1174-1234) +
+ * importYCbCr (internal/lossy/encode.go:544-585, through
+ * lossy.NewEncoderFromYUV :500-539): n RGBA images (w x h, row pitch `stride`
+ * >= 4*w, image pitch rgba_pitch; alpha ignored) -> SharpYUV (WebP matrix,
+ * sRGB transfer, sharp enabled; section 4) -> the encoder's padded planes,
+ * destination rules as wg_import_rgba.  work: wg_sharpyuv_work_bytes(w, h,
+ * n_images), 16-byte aligned; wg_sharpyuv_iterations reads it afterwards. */
+int wg_sharpyuv_import_rgba(const uint8_t* rgba, int32_t w, int32_t h, int32_t stride, int64_t rgba_pitch,
+                            uint8_t* y, uint8_t* u, uint8_t* v, int64_t y_pitch, int64_t uv_pitch,
+                            int32_t n_images, void* work, void* stream);
 
 /* Dithered import (webp.Encode Preprocessing bit 1): importImage's dithered
  * path (internal/lossy/encode.go:690-695, :793-809, :903-940:

@@ -17,6 +17,10 @@
 // 2x4 B of Y and 2 B each of U and V per row pair.  Gamma tables (yuv.go:193-215) are built on the host with
 // float64 pow, passed in the kernel argument block and staged in LDS.
 // Padding replicates the last column / row exactly as the reference's clamp.
+//
+// k_import_ycbcr (further down) is the other way into the encoder's planes:
+// VP8Encoder.importYCbCr (encode.go:544-585), the padding alone, for planes
+// SharpYUV made (webp.Encode's UseSharpYUV).
 #include <math.h>
 #include <string.h>
 
@@ -267,6 +271,260 @@ extern "C" int wg_dither_plan(int32_t w, int32_t h, void* plan, void* stream) {
       hipStreamSynchronize(s) != hipSuccess)
     return wg::check_launch("wg_dither_plan copy");
   return WG_OK;
+}
+
+// ---------------------------------------------------------------------------
+// importYCbCr (internal/lossy/encode.go:544-585): 4:2:0 planes someone else
+// made (sharpyuv.Convert for UseSharpYUV) into the encoder's padded planes.
+// The reference clamps the source index per byte (srcX = min(x, w - 1), srcY
+// = min(y, h - 1), per plane); here one thread makes a 16-byte span of a
+// padded row, so a wave's loads and stores are one contiguous 1 KB each.
+//
+// Rows walked: per image the padded Y rows [ry0, padh), then the chroma rows
+// [rc0, padh / 2), a chroma row holding U's spans and then V's (so Y and
+// chroma rows are about as wide, and the three planes go in one launch).
+// Copy mode walks every row (ry0 = rc0 = 0).  In place (source == the padded
+// planes themselves) only the margin is stored to: the rows below the image
+// are walked the same way (ry0 = h, rc0 = (h + 1) / 2), and the columns right
+// of it -- less than one span wide in every plane -- by the blocks past
+// row_blocks, one thread per row.  Every byte read is an interior byte (column
+// < w of a row < h), which no thread stores to, so in place has no ordering
+// hazard.  No LDS, no scratch.
+namespace {
+struct YCbCrArgs {
+  const uint8_t *sy, *su, *sv;
+  uint8_t *y, *u, *v;
+  int64_t sy_pitch, suv_pitch, y_pitch, uv_pitch;
+  int sy_stride, suv_stride;
+  int w, h, cw, ch;   // source plane sizes
+  int padw, padh;     // padded Y plane (chroma: half of each)
+  int ys, cs;         // 16-byte spans of a padded Y row / of one plane's chroma row (the last may be 8 bytes)
+  int ry0, rc0;       // first row walked of Y / of the chroma planes
+  int rows_img;       // rows walked per image: (padh - ry0) + (padh / 2 - rc0)
+  int rows;           // n_images * rows_img
+  int rp;             // rows walked per block (grid.y stays <= 65535)
+  int tx_log2;        // a block is 2^tx_log2 spans wide and YC_T >> tx_log2 rows deep
+  int row_blocks;     // grid.y blocks that walk rows; the ones above take the column margin (in place)
+  int edges_img;      // in place: rows with a column margin per image, h (Y) + 2 * ch (U, V); else 0
+  int64_t edges;      // n_images * edges_img
+};
+
+constexpr int YC_T = 256;  // threads per block: up to 256 spans = 4096 columns of a row; rows narrower than
+                           // that share a block (1920 columns: 128 spans x 2 rows), so few lanes idle
+constexpr int YC_RP = 8;   // minimum rows walked per thread
+
+// 16 (or 8: NB) clamped source bytes of row `srow` (ws wide) from column x0,
+// as little-endian words.  An interior span is gathered with the widest loads
+// its address allows, the span holding column ws - 1 and the margin byte by
+// byte (a margin span is one byte, replicated).
+template <int NB>
+__device__ __forceinline__ void yc_gather(const uint8_t* srow, int ws, int x0, uint32_t (&v)[4]) {
+  constexpr int NW = NB / 4;
+  if (x0 + NB <= ws) {
+    const uint8_t* p = srow + x0;
+    const uintptr_t al = reinterpret_cast<uintptr_t>(p);
+    if (NB == 16 && (al & 15) == 0) {
+      const uint4 q = *reinterpret_cast<const uint4*>(p);
+      v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+    } else if ((al & 7) == 0) {
+#pragma unroll
+      for (int k = 0; k < NW / 2; k++) {
+        const uint2 q = reinterpret_cast<const uint2*>(p)[k];
+        v[2 * k] = q.x; v[2 * k + 1] = q.y;
+      }
+    } else if ((al & 3) == 0) {
+#pragma unroll
+      for (int k = 0; k < NW; k++) v[k] = reinterpret_cast<const uint32_t*>(p)[k];
+    } else if ((al & 1) == 0) {
+#pragma unroll
+      for (int k = 0; k < NW; k++) {
+        const uint32_t lo = reinterpret_cast<const uint16_t*>(p)[2 * k], hi = reinterpret_cast<const uint16_t*>(p)[2 * k + 1];
+        v[k] = lo | hi << 16;
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < NW; k++)
+        v[k] = (uint32_t)p[4 * k] | (uint32_t)p[4 * k + 1] << 8 | (uint32_t)p[4 * k + 2] << 16 | (uint32_t)p[4 * k + 3] << 24;
+    }
+    return;
+  }
+  const uint32_t edge = srow[ws - 1];
+  if (x0 >= ws) {
+#pragma unroll
+    for (int k = 0; k < NW; k++) v[k] = edge * 0x01010101u;
+    return;
+  }
+#pragma unroll
+  for (int k = 0; k < NW; k++) {
+    uint32_t word = 0;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const int x = x0 + 4 * k + i;
+      const uint32_t b = x < ws ? (uint32_t)srow[x] : edge;
+      word |= b << (8 * i);
+    }
+    v[k] = word;
+  }
+}
+
+// One span of one padded row.  margin_only (in place, rows of the image): an
+// interior span is left alone and the span holding column ws - 1 stores its
+// margin bytes only.  drow is 4-byte aligned (the destination rules).
+template <int NB>
+__device__ __forceinline__ void yc_span_nb(const uint8_t* srow, int ws, uint8_t* drow, int x0, bool margin_only) {
+  constexpr int NW = NB / 4;
+  if (margin_only && x0 + NB <= ws) return;
+  uint32_t v[4] = {0, 0, 0, 0};
+  yc_gather<NB>(srow, ws, x0, v);
+  uint8_t* d = drow + x0;
+  if (margin_only && x0 < ws) {
+#pragma unroll
+    for (int i = 0; i < NB; i++)
+      if (x0 + i >= ws) d[i] = (uint8_t)(v[i >> 2] >> (8 * (i & 3)));
+    return;
+  }
+  const uintptr_t al = reinterpret_cast<uintptr_t>(d);
+  if (NB == 16 && (al & 15) == 0) {
+    *reinterpret_cast<uint4*>(d) = make_uint4(v[0], v[1], v[2], v[3]);
+  } else if ((al & 7) == 0) {
+#pragma unroll
+    for (int k = 0; k < NW / 2; k++) reinterpret_cast<uint2*>(d)[k] = make_uint2(v[2 * k], v[2 * k + 1]);
+  } else {
+#pragma unroll
+    for (int k = 0; k < NW; k++) reinterpret_cast<uint32_t*>(d)[k] = v[k];
+  }
+}
+
+// span c of a padded row pw bytes wide (pw a multiple of 8: the last span of
+// an odd-mbw chroma row is 8 bytes)
+__device__ __forceinline__ void yc_span(const uint8_t* srow, int ws, uint8_t* drow, int pw, int c, bool margin_only) {
+  const int x0 = 16 * c;
+  if (x0 + 16 <= pw) yc_span_nb<16>(srow, ws, drow, x0, margin_only);
+  else yc_span_nb<8>(srow, ws, drow, x0, margin_only);
+}
+
+__global__ __launch_bounds__(YC_T) void k_import_ycbcr(const YCbCrArgs a) {
+  const int pcw = a.padw >> 1;
+  if ((int)blockIdx.y >= a.row_blocks) {
+    // in place: the columns right of the image, rows of the image; item =
+    // (image, plane row), the margin is inside the row's last span
+    const int64_t e = ((int64_t)(blockIdx.y - a.row_blocks) * gridDim.x + blockIdx.x) * YC_T + threadIdx.x;
+    if (e >= a.edges) return;
+    const int img = (int)(e / a.edges_img);
+    int r = (int)(e - (int64_t)img * a.edges_img);
+    if (r < a.h) {
+      if (a.w < a.padw) {
+        uint8_t* row = a.y + img * a.y_pitch + (int64_t)r * a.padw;
+        yc_span(a.sy + img * a.sy_pitch + (int64_t)r * a.sy_stride, a.w, row, a.padw, a.ys - 1, true);
+      }
+      return;
+    }
+    r -= a.h;
+    if (a.cw >= pcw) return;
+    const bool second = r >= a.ch;
+    if (second) r -= a.ch;
+    const int64_t so = img * a.suv_pitch + (int64_t)r * a.suv_stride, dof = img * a.uv_pitch + (int64_t)r * pcw;
+    yc_span((second ? a.sv : a.su) + so, a.cw, (second ? a.v : a.u) + dof, pcw, a.cs - 1, true);
+    return;
+  }
+  const int cx = (blockIdx.x << a.tx_log2) + (threadIdx.x & ((1 << a.tx_log2) - 1));
+  const int yrows = a.padh - a.ry0;
+  const int row_end = min((int)(blockIdx.y + 1) * a.rp, a.rows);
+  for (int rr = blockIdx.y * a.rp + (threadIdx.x >> a.tx_log2); rr < row_end; rr += YC_T >> a.tx_log2) {
+    const int img = rr / a.rows_img, ri = rr - img * a.rows_img;
+    if (ri < yrows) {
+      if (cx >= a.ys) continue;
+      const int r = a.ry0 + ri;
+      yc_span(a.sy + img * a.sy_pitch + (int64_t)min(r, a.h - 1) * a.sy_stride, a.w,
+              a.y + img * a.y_pitch + (int64_t)r * a.padw, a.padw, cx, false);
+    } else {
+      if (cx >= 2 * a.cs) continue;
+      const int r = a.rc0 + ri - yrows;
+      const bool second = cx >= a.cs;
+      const int64_t so = img * a.suv_pitch + (int64_t)min(r, a.ch - 1) * a.suv_stride, dof = img * a.uv_pitch + (int64_t)r * pcw;
+      yc_span((second ? a.sv : a.su) + so, a.cw, (second ? a.v : a.u) + dof, pcw, second ? cx - a.cs : cx, false);
+    }
+  }
+}
+
+// [p, p + n) and [q, q + m) share a byte
+bool yc_overlap(const uint8_t* p, int64_t n, const uint8_t* q, int64_t m) {
+  const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+  return a < b + (uintptr_t)m && b < a + (uintptr_t)n;
+}
+}  // namespace
+
+extern "C" int wg_import_ycbcr(const uint8_t* sy, int32_t sy_stride, int64_t sy_pitch, const uint8_t* su,
+                               const uint8_t* sv, int32_t suv_stride, int64_t suv_pitch, int32_t w, int32_t h,
+                               uint8_t* y, uint8_t* u, uint8_t* v, int64_t y_pitch, int64_t uv_pitch, int32_t n_images,
+                               void* stream) {
+  WG_REQUIRE(sy && su && sv && y && u && v);
+  WG_REQUIRE(w > 0 && h > 0 && n_images > 0);
+  const int cw = (w + 1) >> 1, ch = (h + 1) >> 1;
+  const int mbw = (w + 15) >> 4, mbh = (h + 15) >> 4;
+  const int64_t ybytes = (int64_t)256 * mbw * mbh, cbytes = (int64_t)64 * mbw * mbh;
+  const int64_t sy_bytes = (int64_t)(h - 1) * sy_stride + w, sc_bytes = (int64_t)(ch - 1) * suv_stride + cw;
+  WG_REQUIRE(sy_stride >= w && suv_stride >= cw && sy_pitch >= sy_bytes && suv_pitch >= sc_bytes);
+  WG_REQUIRE(((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(u) | reinterpret_cast<uintptr_t>(v)) &
+              3) == 0 && (y_pitch & 7) == 0 && (uv_pitch & 3) == 0);
+  WG_REQUIRE(y_pitch >= ybytes && uv_pitch >= cbytes);
+  const bool in_place = sy == y && su == u && sv == v && sy_stride == 16 * mbw && suv_stride == 8 * mbw &&
+                        sy_pitch == y_pitch && suv_pitch == uv_pitch;
+  if (!in_place) {
+    // the byte ranges the n images of a source plane and of a destination
+    // plane span must be disjoint
+    const int64_t last = n_images - 1;
+    const uint8_t* src[3] = {sy, su, sv};
+    const int64_t src_n[3] = {last * sy_pitch + sy_bytes, last * suv_pitch + sc_bytes, last * suv_pitch + sc_bytes};
+    const uint8_t* dst[3] = {y, u, v};
+    const int64_t dst_n[3] = {last * y_pitch + ybytes, last * uv_pitch + cbytes, last * uv_pitch + cbytes};
+    for (int i = 0; i < 3; i++)
+      for (int j = 0; j < 3; j++)
+        if (yc_overlap(src[i], src_n[i], dst[j], dst_n[j]))
+          return wg::invalid("wg_import_ycbcr: source and destination overlap (in place needs the same pointers, "
+                             "strides 16*mbw / 8*mbw and the same pitches)");
+  }
+  YCbCrArgs a;
+  a.sy = sy;
+  a.su = su;
+  a.sv = sv;
+  a.y = y;
+  a.u = u;
+  a.v = v;
+  a.sy_pitch = sy_pitch;
+  a.suv_pitch = suv_pitch;
+  a.y_pitch = y_pitch;
+  a.uv_pitch = uv_pitch;
+  a.sy_stride = sy_stride;
+  a.suv_stride = suv_stride;
+  a.w = w;
+  a.h = h;
+  a.cw = cw;
+  a.ch = ch;
+  a.padw = 16 * mbw;
+  a.padh = 16 * mbh;
+  a.ys = mbw;
+  a.cs = (mbw + 1) >> 1;
+  a.ry0 = in_place ? h : 0;
+  a.rc0 = in_place ? ch : 0;
+  a.rows_img = (a.padh - a.ry0) + (a.padh / 2 - a.rc0);
+  WG_REQUIRE((int64_t)n_images * a.rows_img < (1ll << 31) / 2);
+  a.rows = n_images * a.rows_img;
+  const int spans = max(a.ys, 2 * a.cs);
+  a.tx_log2 = 0;
+  while ((1 << a.tx_log2) < min(spans, YC_T)) a.tx_log2++;
+  const unsigned gx = wg::blocks_for(spans, 1 << a.tx_log2);
+  a.rp = max(YC_RP * (YC_T >> a.tx_log2), (int)wg::blocks_for(a.rows, 65535 / 2));
+  a.row_blocks = (int)wg::blocks_for(a.rows, a.rp);
+  // (the chroma margin is empty whenever the luma one is: w = 16 * mbw)
+  a.edges_img = in_place && w < a.padw ? h + 2 * ch : 0;
+  a.edges = (int64_t)n_images * a.edges_img;
+  const int64_t edge_blocks = (a.edges + (int64_t)gx * YC_T - 1) / ((int64_t)gx * YC_T);
+  WG_REQUIRE(edge_blocks <= 65535 / 2);
+  if (a.row_blocks + edge_blocks == 0) return WG_OK;  // in place, no margin
+  const dim3 grid(gx, (unsigned)(a.row_blocks + edge_blocks));
+  hipLaunchKernelGGL(k_import_ycbcr, grid, dim3(YC_T), 0, wg::as_stream(stream), a);
+  return wg::check_launch("k_import_ycbcr");
 }
 
 extern "C" int wg_import_rgba_dithered(const uint8_t* rgba, int32_t w, int32_t h, int32_t stride, int64_t rgba_pitch,

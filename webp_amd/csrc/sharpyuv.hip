@@ -73,6 +73,7 @@ struct SharpArgs {
   const uint8_t* rgb;
   int64_t rgb_pitch;
   int rgb_stride, width, height, w, h, uvw, uvh, uv_rs;
+  int step;             // bytes per pixel: 3 (packed RGB) or 4 (RGBA, the 4th byte ignored)
   uint16_t* best_y;     // state 0 of image 0; state s of image i at + i * img_elems_y + s * state_y
   uint16_t* target_y;   // image i at + i * img_elems_y
   int16_t* best_uv;
@@ -117,7 +118,7 @@ __global__ __launch_bounds__(256) void k_sharp_init(SharpArgs a, int n_img) {
     const int row = (j + r < a.height) ? j + r : j;  // odd height: last row pair repeats the row
     for (int k = 0; k < 2; k++) {
       const int x = min(2 * i + k, a.width - 1);  // odd width: replicate the last pixel
-      const uint8_t* px = rgb + (int64_t)row * a.rgb_stride + 3 * x;
+      const uint8_t* px = rgb + (int64_t)row * a.rgb_stride + a.step * x;
       const bool in = WG_CHK(px, 3, a.rgb, (int64_t)n_img * a.rgb_pitch, "k_sharp_init rgb");
       c[r][k][0] = in ? px[0] << SFIX : 0;
       c[r][k][1] = in ? px[1] << SFIX : 0;
@@ -673,6 +674,7 @@ struct StdArgs {
   uint8_t *y, *u, *v;
   int64_t rgb_pitch, y_pitch, uv_pitch;
   int rgb_stride, y_stride, uv_stride, width, height, uvw, uvh;
+  int step;  // bytes per pixel, as SharpArgs
   int m[12];
 };
 __device__ __forceinline__ int yuv_comp(int r, int g, int b, const int* c) {
@@ -694,7 +696,7 @@ __global__ __launch_bounds__(256) void k_sharp_standard(StdArgs a, int n_img) {
     for (int dx = 0; dx < 2; dx++) {
       const int xx = 2 * i + dx;
       if (xx >= a.width) continue;
-      const uint8_t* px = rgb + (int64_t)yy * a.rgb_stride + 3 * xx;
+      const uint8_t* px = rgb + (int64_t)yy * a.rgb_stride + a.step * xx;
       sr += px[0];
       sg += px[1];
       sb += px[2];
@@ -752,15 +754,17 @@ extern "C" size_t wg_sharpyuv_work_bytes(int32_t width, int32_t height, int32_t 
          WG_IF_TIMELINES(+(size_t)n_images * 4 * nb * 64);
 }
 
-extern "C" int wg_sharpyuv_convert_ex(const uint8_t* rgb, int32_t width, int32_t height, int32_t rgb_stride,
-                                      int64_t rgb_pitch, const int32_t* matrix_host, int32_t transfer,
-                                      int32_t sharp_enabled, int32_t n_images, uint8_t* y, int32_t y_stride,
-                                      int64_t y_pitch, uint8_t* u, uint8_t* v, int32_t uv_stride, int64_t uv_pitch,
-                                      void* work, void* stream) {
+namespace {
+// sharpyuv.Convert over pixels `step` bytes apart (3: packed RGB; 4: RGBA with
+// the alpha byte ignored, sharpYUVConvert's input, encode.go:1174-1234)
+int sharp_convert(const uint8_t* rgb, int32_t step, int32_t width, int32_t height, int32_t rgb_stride,
+                  int64_t rgb_pitch, const int32_t* matrix_host, int32_t transfer, int32_t sharp_enabled,
+                  int32_t n_images, uint8_t* y, int32_t y_stride, int64_t y_pitch, uint8_t* u, uint8_t* v,
+                  int32_t uv_stride, int64_t uv_pitch, void* work, void* stream, const char* entry) {
   WG_REQUIRE(rgb && matrix_host && y && u && v && width > 0 && height > 0 && n_images > 0);
   // (the walk's in-plane byte offsets are 32-bit: 2 B a pixel, < 2^31)
   WG_REQUIRE((int64_t)((width + 1) & ~1) * ((height + 1) & ~1) < (1ll << 30));
-  WG_REQUIRE(rgb_stride >= 3 * width && y_stride >= width && uv_stride >= (width + 1) / 2);
+  WG_REQUIRE(rgb_stride >= step * width && y_stride >= width && uv_stride >= (width + 1) / 2);
   hipStream_t s = wg::as_stream(stream);
   if (!sharp_enabled) {  // convertStandard (sharpyuv.go:68-115)
     StdArgs sa;
@@ -772,6 +776,7 @@ extern "C" int wg_sharpyuv_convert_ex(const uint8_t* rgb, int32_t width, int32_t
     sa.y_pitch = y_pitch;
     sa.uv_pitch = uv_pitch;
     sa.rgb_stride = rgb_stride;
+    sa.step = step;
     sa.y_stride = y_stride;
     sa.uv_stride = uv_stride;
     sa.width = width;
@@ -790,7 +795,7 @@ extern "C" int wg_sharpyuv_convert_ex(const uint8_t* rgb, int32_t width, int32_t
   const int uvw = w / 2, uvh = h / 2;
   const int nb = sharp_bands(width);
   int dev = 0, lut_n = 0;  // (the tables and the resident-workgroup bound below are this device's)
-  if (const int rc = wg::call_device(s, "wg_sharpyuv_convert_ex", &dev)) return rc;
+  if (const int rc = wg::call_device(s, entry, &dev)) return rc;
   const void* tabs = wg::sharpyuv_tables_device(dev, transfer, &lut_n);
   if (!tabs) return WG_EHIP;
   const bool lut = transfer != 13;
@@ -800,6 +805,7 @@ extern "C" int wg_sharpyuv_convert_ex(const uint8_t* rgb, int32_t width, int32_t
   a.rgb = rgb;
   a.rgb_pitch = rgb_pitch;
   a.rgb_stride = rgb_stride;
+  a.step = step;
   a.width = width;
   a.height = height;
   a.w = w;
@@ -898,6 +904,41 @@ extern "C" int wg_sharpyuv_convert_ex(const uint8_t* rgb, int32_t width, int32_t
   const int64_t px = (int64_t)width * height * n_images;
   hipLaunchKernelGGL(k_sharp_final, dim3(wg::blocks_for(px, 256)), dim3(256), 0, s, f, n_images);
   return wg::check_launch("k_sharp_final");
+}
+}  // namespace
+
+extern "C" int wg_sharpyuv_convert_ex(const uint8_t* rgb, int32_t width, int32_t height, int32_t rgb_stride,
+                                      int64_t rgb_pitch, const int32_t* matrix_host, int32_t transfer,
+                                      int32_t sharp_enabled, int32_t n_images, uint8_t* y, int32_t y_stride,
+                                      int64_t y_pitch, uint8_t* u, uint8_t* v, int32_t uv_stride, int64_t uv_pitch,
+                                      void* work, void* stream) {
+  return sharp_convert(rgb, 3, width, height, rgb_stride, rgb_pitch, matrix_host, transfer, sharp_enabled, n_images, y,
+                       y_stride, y_pitch, u, v, uv_stride, uv_pitch, work, stream, "wg_sharpyuv_convert_ex");
+}
+
+// sharpYUVConvert (encode.go:1174-1234: alpha dropped, sharpyuv.Convert with
+// the default options = WebP matrix, sRGB, sharp) writing straight into the
+// encoder's padded planes, then importYCbCr's replication
+// (internal/lossy/encode.go:544-585) of the margin in place.
+extern "C" int wg_sharpyuv_import_rgba(const uint8_t* rgba, int32_t w, int32_t h, int32_t stride, int64_t rgba_pitch,
+                                       uint8_t* y, uint8_t* u, uint8_t* v, int64_t y_pitch, int64_t uv_pitch,
+                                       int32_t n_images, void* work, void* stream) {
+  WG_REQUIRE(rgba && y && u && v && work);
+  WG_REQUIRE(w > 0 && h > 0 && n_images > 0 && stride >= 4 * w);
+  WG_REQUIRE(rgba_pitch >= (int64_t)(h - 1) * stride + 4 * (int64_t)w);
+  const int mbw = (w + 15) >> 4, mbh = (h + 15) >> 4;
+  // (the destination rules of wg_import_rgba)
+  WG_REQUIRE(((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(u) | reinterpret_cast<uintptr_t>(v)) &
+              3) == 0 && (y_pitch & 7) == 0 && (uv_pitch & 3) == 0);
+  WG_REQUIRE(y_pitch >= (int64_t)256 * mbw * mbh && uv_pitch >= (int64_t)64 * mbw * mbh);
+  // kWebpMatrix, sharpyuv/csp.go:66-70
+  static const int32_t kWebp[12] = {16839, 33059, 6420, 16 << 16, -9719, -19081, 28800, 128 << 16,
+                                    28800, -24116, -4684, 128 << 16};
+  const int rc = sharp_convert(rgba, 4, w, h, stride, rgba_pitch, kWebp, 13, 1, n_images, y, 16 * mbw, y_pitch, u, v,
+                               8 * mbw, uv_pitch, work, stream, "wg_sharpyuv_import_rgba");
+  if (rc != WG_OK) return rc;
+  return wg_import_ycbcr(y, 16 * mbw, y_pitch, u, v, 8 * mbw, uv_pitch, w, h, y, u, v, y_pitch, uv_pitch, n_images,
+                         stream);
 }
 
 extern "C" int wg_sharpyuv_convert(const uint8_t* rgb, int32_t width, int32_t height, int32_t rgb_stride,

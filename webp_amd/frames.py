@@ -2,6 +2,8 @@
 
   decode_frames     internal/lossy/decode.go:532-560 (reconstructRow + filterRowAt)
   import_rgba       internal/lossy/encode.go:671-943 (importImage)
+  import_ycbcr      internal/lossy/encode.go:544-585 (importYCbCr)
+  sharpyuv_import_rgba  encode.go:1174-1234 (sharpYUVConvert) + importYCbCr
   analysis_alphas   internal/lossy/encode_analysis.go:245-307 (computeAlphas)
   build_nrgba       webp.go:379-450 (buildNRGBA -> UpsampleLinePairNRGBA)
   plane_ssim        AccumulateSSIM over ssim.go:116-160
@@ -72,6 +74,50 @@ def import_rgba(rgba, has_alpha=True, out=None):
         Y, U, V = out
     call("wg_import_rgba", rgba.data_ptr(), w, h, 4 * w, 4 * w * h, int(bool(has_alpha)), Y.data_ptr(), U.data_ptr(),
          V.data_ptr(), Y[0].numel(), U[0].numel(), n, _stream())
+    return Y, U, V
+
+
+def _padded_planes(n, w, h, device):
+    mbw, mbh = mb_dims(w, h)
+    Y = torch.empty((n, 16 * mbh, 16 * mbw), dtype=torch.uint8, device=device)
+    U = torch.empty((n, 8 * mbh, 8 * mbw), dtype=torch.uint8, device=device)
+    return Y, U, torch.empty_like(U)
+
+
+def import_ycbcr(Y, U, V, out=None):
+    """importYCbCr: unpadded 4:2:0 planes Y (n, h, w), U, V (n, (h+1)//2, (w+1)//2)
+    (CUDA uint8; rows and images may be strided, bytes of a row contiguous; U
+    and V with the same strides) -> the encoder's padded (Y, U, V), the last
+    column and row replicated.  With Y, U, V the [:, :h, :w] / [:, :ch, :cw]
+    views of `out` itself only the margin is filled, in place."""
+    assert Y.is_cuda and Y.dtype == torch.uint8 and Y.dim() == 3 and U.dim() == 3 and V.dim() == 3
+    n, h, w = Y.shape
+    assert tuple(U.shape) == (n, (h + 1) // 2, (w + 1) // 2) and V.shape == U.shape and U.dtype == V.dtype == torch.uint8
+    assert Y.stride(2) == 1 and U.stride(2) == 1 and U.stride() == V.stride()
+    pY, pU, pV = _padded_planes(n, w, h, Y.device) if out is None else out
+    assert pY.is_contiguous() and pU.is_contiguous() and pV.is_contiguous()
+    call("wg_import_ycbcr", Y.data_ptr(), Y.stride(1), Y.stride(0), U.data_ptr(), V.data_ptr(), U.stride(1), U.stride(0),
+         w, h, pY.data_ptr(), pU.data_ptr(), pV.data_ptr(), pY[0].numel(), pU[0].numel(), n, _stream())
+    return pY, pU, pV
+
+
+def sharpyuv_import_rgba(rgba, out=None, work=None, iterations=False):
+    """webp.Encode's UseSharpYUV import (sharpYUVConvert + NewEncoderFromYUV's
+    importYCbCr): (n, h, w, 4) uint8 RGBA, alpha ignored -> padded (Y, U, V).
+    iterations=True also returns the refinement iterations each image ran
+    (numpy int32; synchronises the stream)."""
+    assert rgba.is_cuda and rgba.dtype == torch.uint8 and rgba.dim() == 4 and rgba.is_contiguous()
+    n, h, w, c = rgba.shape
+    assert c == 4
+    Y, U, V = _padded_planes(n, w, h, rgba.device) if out is None else out
+    if work is None:
+        work = torch.empty(lib.wg_sharpyuv_work_bytes(w, h, n), dtype=torch.uint8, device=rgba.device)
+    call("wg_sharpyuv_import_rgba", rgba.data_ptr(), w, h, 4 * w, 4 * w * h, Y.data_ptr(), U.data_ptr(), V.data_ptr(),
+         Y[0].numel(), U[0].numel(), n, work.data_ptr(), _stream())
+    if iterations:
+        its = np.zeros(n, np.int32)
+        call("wg_sharpyuv_iterations", work.data_ptr(), w, h, n, its.ctypes.data, _stream())
+        return Y, U, V, its
     return Y, U, V
 
 
@@ -358,16 +404,19 @@ def segment_analysis(cfg, alphas, uv_sum, mbw, mbh, out=None, info=True):
     return seg_ids, segs, inf
 
 
-def encode_frames(rgba, cfg=None, has_alpha=False, proba=None, check=True):
+def encode_frames(rgba, cfg=None, has_alpha=False, proba=None, check=True, use_sharp_yuv=False):
     """The lossy encoder's DSP path for n same-sized RGBA frames, as
     NewEncoder + EncodeFrame run it up to Phase A (internal/lossy/encode.go:452,
     :1324-1366): importImage -> computeAlphas -> analysis() segments ->
     encodeFrameParallel Phase A.  Everything stays on the device.
+    use_sharp_yuv: EncoderOptions.UseSharpYUV -- the import step is
+    sharpYUVConvert + NewEncoderFromYUV's importYCbCr (alpha ignored) instead
+    of importImage; nothing else changes.
     Returns (mb_enc bytes (n*mbw*mbh, 864), (RY, RU, RV), seg_ids, segs, info)."""
     n, h, w, _ = rgba.shape
     mbw, mbh = mb_dims(w, h)
     cfg = encoder_config() if cfg is None else cfg
-    Y, U, V = import_rgba(rgba, has_alpha=has_alpha)
+    Y, U, V = sharpyuv_import_rgba(rgba) if use_sharp_yuv else import_rgba(rgba, has_alpha=has_alpha)
     alphas, uv_sum = analysis_alphas(Y, U, V, w, h)
     seg_ids, segs, info = segment_analysis(cfg, alphas, uv_sum, mbw, mbh)
     if proba is None:
