@@ -373,6 +373,67 @@ int wg_encode_frames_devices(const int32_t* devices, int32_t n_devices, const ui
  * uploaded by wg_encode_mbs; host memory, 1000 uint16. */
 int wg_fixed_costs_i4_host(uint16_t* out);
 
+/* Phase B of encodeFrameParallel on the device, for methods 3-6 without rate
+ * control (internal/lossy/encode.go:1356-1385): token statistics, optimizeProba
+ * and the token stream from wg_encode_mbs's records, then a host emitter.
+ * What partition 0 and the emitter need per macroblock; 32 bytes. */
+typedef struct wg_mb_hdr {
+  uint8_t modes[16];              /* wg_mb_enc.modes, copied */
+  uint8_t mb_type, i16_mode, uv_mode, skip, segment, pad[3];
+  uint32_t tok_start, tok_count;  /* this MB's tokens, in tokens, relative to the image's token base */
+} wg_mb_hdr;
+typedef struct wg_token_summary { /* per image; 16 bytes */
+  uint32_t total_tokens, num_skip, num_updates; /* num_updates: optimizeProba's return value */
+  uint8_t skip_proba, pad[3];     /* encode_parallel.go:1595-1597 when num_skip > 0, else 0 */
+} wg_token_summary;
+/* Device scratch of wg_encode_token_stats (16-byte aligned). */
+size_t wg_encode_tokens_work_bytes(int32_t mbw, int32_t mbh, int32_t n_images);
+/* recordAllTokens' statistics (collectMBStats over every non-skipped MB,
+ * encode_parallel.go:1503-1707; collectCoeffStats / collectLevelStats
+ * encode_proba.go:10-113), optimizeProba (encode_proba.go:117-168) and the
+ * per-MB token counts of recordMBTokens (encode_frame.go:647-759) with their
+ * exclusive scan, for n images of mbw x mbh records (wg_mb_enc [n][mbh][mbw],
+ * 16-byte aligned).  The non-zero counts are read from the records.
+ * proba_in: [1056] coefficient probabilities, proba_in_pitch bytes apart per
+ * image (0: one table for all).  stats: uint32 [n][4][8][3][11][2] =
+ * [type][band][ctx][proba][bit] (may be NULL).  proba_out [n][1056] starts as
+ * proba_in; an entry is replaced where optimizeProba replaces it (the old cost
+ * is priced against CoeffsProba0, as there).  hdr [n][mbh*mbw], summary [n].
+ * Several launches on `stream`, none of which waits on another workgroup.
+ * WG_EINVAL when mbw*mbh*7600 (the most tokens a frame can have: 25 blocks x
+ * 16 coefficients x 19 tokens) does not fit in 32 bits. */
+int wg_encode_token_stats(const void* mb_enc, int32_t mbw, int32_t mbh, int32_t n_images,
+                          const uint8_t* proba_in, int64_t proba_in_pitch, uint32_t* stats, uint8_t* proba_out,
+                          wg_mb_hdr* hdr, wg_token_summary* summary, void* work, void* stream);
+/* recordMBTokens / RecordCoeffs / recordLevelVP8 (encode_frame.go:647-759,
+ * encode_token.go:115-300) over every non-skipped MB with `proba` ([n][1056],
+ * wg_encode_token_stats's proba_out), which makes rerecordAllTokens
+ * (encode_proba.go:317-353) unnecessary: Token{Bit, Prob} byte pairs
+ * (encode_token.go:15-18), MB i's at tokens + img*tokens_pitch +
+ * 2*hdr[i].tok_start.  tokens 4-byte aligned, tokens_pitch (bytes per image)
+ * a multiple of 4; an MB whose range would pass tokens_pitch writes nothing.
+ * hdr and work as wg_encode_token_stats left them (work keeps the MBs'
+ * contexts), after it on the same stream. */
+int wg_encode_tokens(const void* mb_enc, int32_t mbw, int32_t mbh, int32_t n_images, const uint8_t* proba,
+                     const wg_mb_hdr* hdr, const void* work, uint8_t* tokens, int64_t tokens_pitch, void* stream);
+/* HOST memory in and out, no device work: emitFrame (+ AssembleRIFF when
+ * riff != 0) for one image (encode_syntax.go:27-172, :511-538; the bool
+ * writer is internal/bitio/writer_bool.go): partition 0 (segment header from
+ * `info` as buildSegmentHeader sets it encode_analysis.go:852-868, filter
+ * header from cfg and info->filter_level encode.go:1276-1319, quantiser
+ * base_quant / dq_uv_dc / dq_uv_ac, writeCoeffProba, skip flag, writeMBModes
+ * :325-500), then 1 << log2_parts token partitions, MB row y in partition
+ * y & (parts - 1) (encode_token.go:322-361).  hdr / proba / summary / tokens:
+ * host copies of one image's outputs above, hdr [mbh*mbw]; mbw, mbh must be
+ * the macroblock counts of width x height (WG_EINVAL otherwise).  *out_size
+ * is set to the file's size whenever that is known, also with WG_ENOMEM
+ * (out_cap too small; nothing is written then).  wg_vp8_emit_bound: an upper
+ * bound of that size (every bool-coded symbol costs at most one byte). */
+size_t wg_vp8_emit_bound(int32_t mbw, int32_t mbh, uint32_t total_tokens);
+int wg_vp8_emit(int32_t width, int32_t height, int32_t mbw, int32_t mbh, const wg_enc_config* cfg,
+                const wg_frame_segs* info, const wg_mb_hdr* hdr, const uint8_t* proba, const wg_token_summary* summary, const uint8_t* tokens,
+                int32_t log2_parts, int32_t riff, uint8_t* out, size_t out_cap, size_t* out_size);
+
 /* After wg_decode_frames on the same stream: WG_OK, or WG_EHIP if a row
  * dependency wait of the last launch on `work`, or of any decoder launch since
  * the library loaded, timed out inside the kernel (output invalid).

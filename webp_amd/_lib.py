@@ -131,6 +131,11 @@ SIGNATURES = {
     "wg_segment_analysis": [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _vp],
     "wg_encode_status": [_vp, _i32, _i32, _vp],
     "wg_encode_row_order": [_vp, _i32, _i32, _i32, _vp, _vp],
+    "wg_encode_tokens_work_bytes": [_i32, _i32, _i32],
+    "wg_encode_token_stats": [_vp, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp],
+    "wg_encode_tokens": [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp],
+    "wg_vp8_emit_bound": [_i32, _i32, ctypes.c_uint32],
+    "wg_vp8_emit": [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, ctypes.c_size_t, _vp],
     "wg_encode_frames_devices": [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "wg_vp8l_residual_image_devices": [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp],
     "wg_plane_ssim_devices": [_vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _vp],
@@ -140,6 +145,7 @@ _RES = {"wg_last_error": ctypes.c_char_p, "wg_decode_work_bytes": ctypes.c_size_
         "wg_sharpyuv_work_bytes": ctypes.c_size_t, "wg_encode_work_bytes": ctypes.c_size_t,
         "wg_alpha_unfilter_work_bytes": ctypes.c_size_t, "wg_alpha_estimate_work_bytes": ctypes.c_size_t,
         "wg_rescaler_plan_bytes": ctypes.c_size_t, "wg_dither_plan_bytes": ctypes.c_size_t,
+        "wg_encode_tokens_work_bytes": ctypes.c_size_t, "wg_vp8_emit_bound": ctypes.c_size_t,
         "wg_dither_amp": ctypes.c_int32, "wg_random_init_host": None}
 
 for _name, _args in SIGNATURES.items():

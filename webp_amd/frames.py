@@ -7,10 +7,15 @@
   analysis_alphas   internal/lossy/encode_analysis.go:245-307 (computeAlphas)
   build_nrgba       webp.go:379-450 (buildNRGBA -> UpsampleLinePairNRGBA)
   plane_ssim        AccumulateSSIM over ssim.go:116-160
+  encode_tokens     encode_parallel.go:1503-1707, encode_proba.go:117-168 (Phase B)
+  vp8_emit          internal/lossy/encode_syntax.go:27-172, :511 (emitFrame, host)
+  encode_webp       encode_frames -> encode_tokens -> vp8_emit
 
 All take / return CUDA tensors; a leading batch dimension means "n images of
 the same size".  Everything runs in libwebpgpu.so on the GPU.
 """
+import ctypes
+
 import numpy as np
 import torch
 
@@ -436,3 +441,96 @@ def default_proba(device="cuda"):
     body = txt[txt.index("vp8_coeffs_proba0["):]
     body = body[body.index("{") + 1:body.index("};")]
     return torch.tensor([int(x) for x in re.findall(r"\d+", body)], dtype=torch.uint8, device=device)
+
+
+# ---------------- Phase B: token statistics, probabilities, tokens, VP8 writer ----------------
+
+MB_HDR_DTYPE = np.dtype([("modes", "u1", (16,)), ("mb_type", "u1"), ("i16_mode", "u1"), ("uv_mode", "u1"),
+                         ("skip", "u1"), ("segment", "u1"), ("pad", "u1", (3,)), ("tok_start", "<u4"),
+                         ("tok_count", "<u4")])  # wg_mb_hdr
+TOKEN_SUMMARY_DTYPE = np.dtype([("total_tokens", "<u4"), ("num_skip", "<u4"), ("num_updates", "<u4"),
+                                ("skip_proba", "u1"), ("pad", "u1", (3,))])  # wg_token_summary
+assert MB_HDR_DTYPE.itemsize == 32 and TOKEN_SUMMARY_DTYPE.itemsize == 16
+NUM_PROBAS = 4 * 8 * 3 * 11
+
+
+def encode_tokens(mb_enc, mbw, mbh, proba=None, tokens_pitch=None):
+    """Phase B on the device (recordAllTokens' statistics + optimizeProba +
+    recordMBTokens with the optimised table, internal/lossy/encode.go:1356-1385)
+    over n images of wg_mb_enc records: mb_enc (n*mbh*mbw, 864) uint8 CUDA;
+    proba None (CoeffsProba0), (1056,) or (n, 1056) uint8.
+    Returns (hdr (n, mbh*mbw, 32) uint8, proba_out (n, 1056) uint8, summary
+    (n,) TOKEN_SUMMARY_DTYPE numpy, tokens (n, pitch) uint8 {bit, prob} pairs,
+    stats (n, 4, 8, 3, 11, 2) int32 holding the uint32 counters), all but
+    summary CUDA tensors.  Synchronises to read the totals and size `tokens`
+    exactly (the largest image's count, rounded up to a dword); a given
+    tokens_pitch (bytes, a multiple of 4) is used as it is."""
+    assert mb_enc.is_cuda and mb_enc.dtype == torch.uint8 and mb_enc.is_contiguous()
+    nmb = mbw * mbh
+    n = mb_enc.numel() // (MB_ENC_DTYPE.itemsize * nmb)
+    assert n >= 1 and mb_enc.numel() == n * nmb * MB_ENC_DTYPE.itemsize
+    dev = mb_enc.device
+    if proba is None:
+        proba = default_proba(dev)
+    elif not torch.is_tensor(proba):
+        proba = torch.from_numpy(np.ascontiguousarray(proba, np.uint8)).to(dev)
+    proba = proba.contiguous()
+    assert proba.dtype == torch.uint8 and proba.numel() in (NUM_PROBAS, n * NUM_PROBAS)
+    pitch_in = 0 if proba.numel() == NUM_PROBAS else NUM_PROBAS
+    work = torch.empty(lib.wg_encode_tokens_work_bytes(mbw, mbh, n), dtype=torch.uint8, device=dev)
+    stats = torch.empty((n, 4, 8, 3, 11, 2), dtype=torch.int32, device=dev)
+    proba_out = torch.empty((n, NUM_PROBAS), dtype=torch.uint8, device=dev)
+    hdr = torch.empty((n, nmb, MB_HDR_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+    summary = torch.empty((n, TOKEN_SUMMARY_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+    call("wg_encode_token_stats", mb_enc.data_ptr(), mbw, mbh, n, proba.data_ptr(), pitch_in, stats.data_ptr(),
+         proba_out.data_ptr(), hdr.data_ptr(), summary.data_ptr(), work.data_ptr(), _stream())
+    summ = summary.cpu().numpy().view(TOKEN_SUMMARY_DTYPE).reshape(n)  # synchronises
+    if tokens_pitch is None:
+        tokens_pitch = (2 * int(summ["total_tokens"].max()) + 3) & ~3
+    tokens = torch.empty((n, tokens_pitch), dtype=torch.uint8, device=dev)
+    call("wg_encode_tokens", mb_enc.data_ptr(), mbw, mbh, n, proba_out.data_ptr(), hdr.data_ptr(), work.data_ptr(),
+         tokens.data_ptr() if tokens_pitch else None, tokens_pitch, _stream())
+    return hdr, proba_out, summ, tokens, stats
+
+
+def vp8_emit(width, height, cfg, info, hdr, proba, summary, tokens, log2_parts=0, riff=True):
+    """emitFrame (+ AssembleRIFF) on the host for one image (wg_vp8_emit): cfg
+    ENC_CONFIG_DTYPE, info FRAME_SEGS_DTYPE record, hdr (mbh*mbw,) MB_HDR_DTYPE,
+    proba (1056,) uint8, summary TOKEN_SUMMARY_DTYPE record, tokens uint8
+    {bit, prob} pairs -- numpy (host) arrays.  Returns bytes."""
+    mbw, mbh = mb_dims(width, height)
+    cfg = np.ascontiguousarray(cfg, ENC_CONFIG_DTYPE).reshape(-1)[:1]
+    info = np.ascontiguousarray(info).view(np.uint8).reshape(-1)
+    assert info.size == FRAME_SEGS_DTYPE.itemsize
+    hdr = np.ascontiguousarray(hdr).view(np.uint8).reshape(-1)
+    assert hdr.size == mbw * mbh * MB_HDR_DTYPE.itemsize
+    proba = np.ascontiguousarray(proba, np.uint8).reshape(-1)
+    assert proba.size == NUM_PROBAS
+    summary = np.ascontiguousarray(summary).view(np.uint8).reshape(-1)
+    assert summary.size == TOKEN_SUMMARY_DTYPE.itemsize
+    total = int(summary.view(TOKEN_SUMMARY_DTYPE)["total_tokens"][0])
+    tokens = np.ascontiguousarray(tokens, np.uint8).reshape(-1)
+    assert tokens.size >= 2 * total
+    cap = lib.wg_vp8_emit_bound(mbw, mbh, total)
+    out = np.empty(cap, np.uint8)
+    size = ctypes.c_size_t(0)
+    call("wg_vp8_emit", width, height, mbw, mbh, cfg.ctypes.data, info.ctypes.data, hdr.ctypes.data, proba.ctypes.data,
+         summary.ctypes.data, tokens.ctypes.data if total else None, int(log2_parts), int(bool(riff)), out.ctypes.data,
+         cap, ctypes.byref(size))
+    return out[:size.value].tobytes()
+
+
+def encode_webp(rgba, cfg=None, use_sharp_yuv=False, log2_parts=0):
+    """n same-sized RGBA frames (n, h, w, 4) uint8 CUDA -> n lossy WebP files
+    (bytes), as webp.Encode writes them for methods 3-6 without rate control:
+    encode_frames (import, analysis, Phase A) -> encode_tokens (Phase B) on the
+    device, then the bool coder and the container on the host (vp8_emit)."""
+    n, h, w, _ = rgba.shape
+    mbw, mbh = mb_dims(w, h)
+    cfg = encoder_config() if cfg is None else cfg
+    out, _, _, _, info = encode_frames(rgba, cfg=cfg, use_sharp_yuv=use_sharp_yuv)
+    hdr, proba, summ, tokens, _ = encode_tokens(out, mbw, mbh)
+    hdr, proba, info = hdr.cpu().numpy(), proba.cpu().numpy(), info.cpu().numpy()
+    toks = [tokens[i, :2 * int(summ["total_tokens"][i])].cpu().numpy() for i in range(n)]  # each image's own range
+    return [vp8_emit(w, h, cfg, info[i], hdr[i], proba[i], summ[i:i + 1], toks[i], log2_parts=log2_parts)
+            for i in range(n)]
